@@ -258,14 +258,16 @@ def _wgrad(dy: torch.Tensor, x: torch.Tensor, n_out: int, k_out: int, out=None, 
 # profiles/r06_stream_identity.txt).  All three roles are created together, on first use, in a fixed order.
 # Measured per pool entry (scratch/r06_stream_identity.py: a 108-workgroup wgrad on pool stream k beside an NT GEMM on the default stream,
 # 503 + 281 us alone).  With the runtime's default of four hardware queues: 575 - 600 us together on entries 0 - 5, 7 - 9, 11; 755 - 786 us --
-# nearly serial -- on entries 6 and 10, which land on the default stream's queue.  With GPU_MAX_HW_QUEUES = 8 (what maest_amd/__init__.py sets):
+# nearly serial -- on entries 6 and 10, which land on the default stream's queue.  With eight hardware queues (a job's own setting):
 # 585 - 600 us, and 662 - 677 us on entries 3 and 10.  Those entries are passed over (the index is the pool stream's id >> 5); with any other
 # queue count nothing is skipped, and a runtime that maps differently loses nothing.
 _ENGINE_STREAMS = {}
+_RUNTIME_DEFAULT_QUEUES = "4"          # the HIP runtime's count when the environment sets none
 
 
-def _on_default_queue(k: int) -> bool:
-    q = os.environ.get("GPU_MAX_HW_QUEUES", "4")
+def _on_default_queue(k: int, queues=None) -> bool:
+    """Whether pool entry k shares the default stream's hardware queue at `queues` queues (default: the process's count)."""
+    q = str(queues) if queues is not None else os.environ.get("GPU_MAX_HW_QUEUES") or _RUNTIME_DEFAULT_QUEUES
     return (k >= 4 and k % 4 == 2) if q == "4" else (k % 7 == 3) if q == "8" else False
 
 

@@ -58,7 +58,8 @@ def worker(rank, world, port, out, backend):
 
 
 if __name__ == "__main__":
-    out = "/tmp/dp_out"; os.makedirs(out, exist_ok=True)
+    import tempfile
+    out = tempfile.mkdtemp(prefix="maest_dp_")          # (a fresh directory per run: no stale or foreign rank files)
     import socket
     with socket.socket() as sk:                      # a free rendezvous port on this box
         sk.bind(("127.0.0.1", 0))
@@ -66,6 +67,8 @@ if __name__ == "__main__":
     backend = sys.argv[sys.argv.index("--backend") + 1] if "--backend" in sys.argv else "gloo"
     mp.spawn(worker, args=(2, port, out, backend), nprocs=2, join=True)
     r0, r1 = torch.load(f"{out}/rank0.pt"), torch.load(f"{out}/rank1.pt")
+    import shutil
+    shutil.rmtree(out, ignore_errors=True)
     for n in r0["w"]:
         assert torch.equal(r0["w"][n], r1["w"][n]), f"weights diverged across ranks: {n}"
         if n in r0["g"]:
