@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define MAEST_ABI_VERSION 8
+#define MAEST_ABI_VERSION 9
 
 #define MAEST_OK 0
 #define MAEST_ERR_INVALID 1 /* bad argument (shape / alignment / dtype) */
@@ -60,7 +60,7 @@ extern "C" {
 
 /* GEMM epilogues */
 #define MAEST_F16 3 /* IEEE half: accepted as the INPUT dtype of maest_patch_im2col only (the loader's float16 mel batches,
-                       discogs/dataset.py:58-67) */
+                       discogs/dataset.py:58-67), and as the dx dtype of its backward maest_patch_im2col_bwd */
 
 #define MAEST_EPI_NONE 0     /* C = acc + bias                                           */
 #define MAEST_EPI_GELU 1     /* C = gelu_erf(acc+bias) ; aux_out (optional) = gelu_erf'(acc+bias), saved for backward */
@@ -276,6 +276,22 @@ int maest_patch_im2col_strided(const void* x, int x_dtype, int B, int F, int T, 
                                const float* lam, const int32_t* tok_ft, int P, const int32_t* t_stripes, int n_t,
                                const int32_t* f_stripes, int n_f, void* out, int dtype, void* stream);
 
+/* Backward of maest_patch_im2col_strided (ABI 9): the gradient w.r.t. its input x, for a loss that reaches the mel input
+ * through the patch-embedding convolution (autograd of PatchEmbed.forward, models/maest.py:243-256, with the mixup of
+ * models/module.py:77-83 and the SpecMasking of helpers/spec_masking.py:27-33 in front of it).  Every option of the forward:
+ * dcols: dtype [B*P, 256] (MAEST_F32 / MAEST_BF16), the gradient of `out`; stride_f / stride_t, perm / lam, tok_ft, t_stripes /
+ * f_stripes exactly as the forward got them.  dx: x_dtype [B, F, T] (MAEST_F32 or MAEST_F16: the dtype the forward read), fully
+ * written:  dx[c] = lam[c] * g_c + sum_{b : perm[b] == c} (1 - lam[b]) * g_b, where g_b scatters the rows of clip b back onto
+ * the samples they read (no mixup: dx[c] = g_c).  A sample that no kept patch covers, or that lies inside one of clip c's stripes,
+ * gets exactly 0.  tok_ft must list distinct (f, t) positions.  Deterministic: one gather per sample in a fixed order, no atomics.
+ * work: int32 device workspace of work_elems >= Fp * Tp (+ 2 * B + 1 with mixup) elements, Fp = (F - 16) / stride_f + 1,
+ * Tp = (T - 16) / stride_t + 1: the (f, t) -> token lookup and the mixup partner lists are built there on the device, so the
+ * call makes no host round trip.  perm / lam may be NULL together; t_stripes / f_stripes may be NULL with n_t / n_f = 0. */
+int maest_patch_im2col_bwd(const void* dcols, int dtype, int B, int F, int T, int stride_f, int stride_t,
+                           const int32_t* perm, const float* lam, const int32_t* tok_ft, int P, const int32_t* t_stripes,
+                           int n_t, const int32_t* f_stripes, int n_f, int32_t* work, int64_t work_elems, void* dx,
+                           int x_dtype, void* stream);
+
 /* ---- K5 + K6: positional add + token assembly (models/maest.py:645-675, 769, 785-796) ------------
  * patches: fp32 [B*P, 768] (conv output incl. bias); x0: fp32 [B, 2 + P, 768]
  *   x0[b,0] = cls + new_pos[0]; x0[b,1] = dist + new_pos[1];
@@ -304,6 +320,11 @@ int maest_head_pool_bwd(const float* d_cls, const float* d_dist, const float* d_
                         float* dx, float* dgamma, float* dbeta, void* stream);
 /* early-exit embedding (models/maest.py:825-829): emb[b] = cat(x[b,0], x[b,1], mean(x[b,2:], 0)) */
 int maest_embed_pool(const float* x, int B, int N, float* emb, void* stream);
+/* Backward of maest_embed_pool (ABI 9; autograd of the early-exit cat in forward_features, models/maest.py:825-829):
+ * d_emb fp32 [B, 2304] -> dx fp32 [B, N, 768], fully written: rows 0 and 1 get d_emb[:, :768] and d_emb[:, 768:1536], every
+ * token row n >= 2 gets d_emb[:, 1536:] / (N - 2).  dx_lp: the same rows in the 16-bit operand type (dx_lp_dtype = MAEST_BF16)
+ * for the block backward's dgrad GEMM, as maest_layernorm_bwd's dx_lp; may be NULL. */
+int maest_embed_pool_bwd(const float* d_emb, int B, int N, float* dx, void* dx_lp, int dx_lp_dtype, void* stream);
 
 /* ---- K18: BCE-with-logits, mean reduction (models/module.py:90, 299-301) ------------------------
  * loss (fp32 scalar, ACCUMULATED: zero it first) += weight * mean(max(z,0) - z*y + log1p(exp(-|z|)))

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MAEST_HIP_LIB") or os.path.join(_HERE, "libmaest_hip.
 
 F32 = 0
 BF16 = 1
-F16 = 3     # IEEE half, input of maest_patch_im2col only
+F16 = 3     # IEEE half, input of maest_patch_im2col only (and dx of maest_patch_im2col_bwd)
 BF16_QS = 4 # bf16 qkv tensor with q columns pre-multiplied by scale * log2(e) (maest_attn_* dtype only)
 SPLIT3_A, SPLIT3_B, F32X3_A3 = 5, 6, 7   # the split-bf16 product as one bf16 GEMM of 3 K (include/maest_hip.h)
 F32X3 = 2   # fp32 tensors, split-bf16 matrix products (maest_gemm_nt in_dtype / maest_attn_fwd dtype only)
@@ -47,11 +47,13 @@ SIGNATURES = {
     "maest_scatter_head_rows": [_P, _I, _I, _I, _I, _I, _P, _P],
     "maest_patch_im2col": [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P],
     "maest_patch_im2col_strided": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _I, _P],
+    "maest_patch_im2col_bwd": [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _I, _P, _L, _P, _I, _P],
     "maest_token_assemble": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P],
     "maest_token_assemble_bwd": [_P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P],
     "maest_head_pool_fwd": [_P, _I, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P],
     "maest_head_pool_bwd": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "maest_embed_pool": [_P, _I, _I, _P, _P],
+    "maest_embed_pool_bwd": [_P, _I, _I, _P, _P, _I, _P],
     "maest_bce_logits": [_P, _P, _P, _P, _I, _I, _F, _P, _P, _P],
     "maest_sigmoid_mean": [_P, _I, _I, _P, _P],
     "maest_colsum": [_P, _L, _I, _I, _I, _P, _P],
@@ -71,7 +73,7 @@ SIGNATURES = {
 }
 FORM_GEMM_NT_OW, FORM_GEMM_TN_OW, FORM_ATTN_FWD_PW = 1, 2, 4
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 OPTIONS = {"gemm_min_m": 0, "gemm_variant": 1, "gemm_epilogue": 2, "attn_bwd": 3, "ln_bwd_blocks": 4, "gemm_tail": 5, "attn_fwd": 6, "attn_fwd_waves": 7,
            "tn_reduce": 8, "gemm_wgs": 9, "gemm_panel": 10}
 

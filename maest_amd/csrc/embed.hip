@@ -286,6 +286,95 @@ __global__ __launch_bounds__(256) void melfile_assemble_kernel(const uint16_t* _
     }
 }
 
+// ---- backward of patch_im2col_kernel (col2im): the input gradient of the patch embedding's operand.
+// Two launches.  col2im_prep_kernel (ONE workgroup) writes the token lookup lut[f * Tp + t] = j (-1: patch dropped by patchout) and,
+// with mixup, the clips that read clip c as their partner (perm[b] == c) as a CSR list in increasing b: moff[c] .. moff[c + 1] into
+// mlist.  col2im_kernel then GATHERS: one thread per input sample (y, x) of clip c sums, in a fixed order, every operand element that
+// read it -- clip c's own rows (weight lam[c]) first, then each partner's rows (weight 1 - lam[b]), each over the <= ceil(16 / stride)
+// patches per axis that cover the sample.  No atomics: a rerun is bit-identical.  A sample inside one of clip c's SpecMasking stripes
+// gets 0 (the forward read 0.0 there for the clip itself and for every clip that mixed it in); one that no kept patch covers, 0 too.
+__global__ __launch_bounds__(256) void col2im_prep_kernel(const int32_t* __restrict__ tok_ft, int P, int Fp, int Tp,
+                                                          const int32_t* __restrict__ perm, int B, int32_t* __restrict__ lut,
+                                                          int32_t* __restrict__ moff, int32_t* __restrict__ mlist) {
+    const int n = Fp * Tp;
+    for (int i = threadIdx.x; i < n; i += 256) lut[i] = -1;
+    __syncthreads();
+    for (int j = threadIdx.x; j < P; j += 256) {
+        const int f = tok_ft[2 * j], t = tok_ft[2 * j + 1];
+        if (f >= 0 && f < Fp && t >= 0 && t < Tp) lut[f * Tp + t] = j;
+    }
+    if (perm == nullptr) return;
+    for (int c = threadIdx.x; c <= B; c += 256) {
+        int off = 0;                  // partners of the clips before c: the CSR offset of clip c
+        for (int b = 0; b < B; ++b) off += perm[b] >= 0 && perm[b] < c;
+        moff[c] = off;
+        if (c == B) continue;
+        for (int b = 0; b < B; ++b)
+            if (perm[b] == c) mlist[off++] = b;
+    }
+}
+
+__device__ __forceinline__ bool stripe_masked(const int32_t* __restrict__ t_stripes, int n_t,
+                                              const int32_t* __restrict__ f_stripes, int n_f, int b, int y, int x) {
+    for (int k = 0; k < n_f; ++k) {
+        int st = f_stripes[((int64_t)b * n_f + k) * 2];
+        const int w = f_stripes[((int64_t)b * n_f + k) * 2 + 1];
+        st = st < 0 ? 0 : st;
+        if (y >= st && y < st + w) return true;
+    }
+    for (int k = 0; k < n_t; ++k) {
+        int st = t_stripes[((int64_t)b * n_t + k) * 2];
+        const int w = t_stripes[((int64_t)b * n_t + k) * 2 + 1];
+        st = st < 0 ? 0 : st;
+        if (x >= st && x < st + w) return true;
+    }
+    return false;
+}
+
+// grid (ceil(F * T / 256), B): a workgroup covers 256 consecutive samples of one clip
+template <typename GT, typename XT>
+__global__ __launch_bounds__(256) void col2im_kernel(const GT* __restrict__ dcols, int B, int F, int T, int stride_f,
+                                                     int stride_t, int Fp, int Tp, int P, const float* __restrict__ lam,
+                                                     const int32_t* __restrict__ lut, const int32_t* __restrict__ moff,
+                                                     const int32_t* __restrict__ mlist,
+                                                     const int32_t* __restrict__ t_stripes, int n_t,
+                                                     const int32_t* __restrict__ f_stripes, int n_f, XT* __restrict__ dx) {
+    const int c = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= F * T) return;
+    const int y = i / T, x = i - y * T;
+    float sum = 0.0f;
+    if (n_t + n_f == 0 || !stripe_masked(t_stripes, n_t, f_stripes, n_f, c, y, x)) {
+        // patches f with stride_f * f <= y < stride_f * f + 16, likewise t
+        const int f_lo = y >= PE_K ? (y - PE_K + stride_f) / stride_f : 0;
+        const int t_lo = x >= PE_K ? (x - PE_K + stride_t) / stride_t : 0;
+        const int f_hi = y / stride_f < Fp - 1 ? y / stride_f : Fp - 1;
+        const int t_hi = x / stride_t < Tp - 1 ? x / stride_t : Tp - 1;
+        auto gather = [&](int b) {
+            float s = 0.0f;
+            for (int f = f_lo; f <= f_hi; ++f)
+                for (int t = t_lo; t <= t_hi; ++t) {
+                    const int j = lut[f * Tp + t];
+                    if (j < 0) continue;
+                    const GT g = dcols[((int64_t)b * P + j) * 256 + (y - f * stride_f) * PE_K + (x - t * stride_t)];
+                    if constexpr (sizeof(GT) == 2) s += bf2f(g);
+                    else s += g;
+                }
+            return s;
+        };
+        if (lam == nullptr) {
+            sum = gather(c);
+        } else {
+            sum = lam[c] * gather(c);
+            for (int k = moff[c]; k < moff[c + 1]; ++k) {
+                const int b = mlist[k];
+                sum += (1.0f - lam[b]) * gather(b);
+            }
+        }
+    }
+    dx[(int64_t)c * F * T + i] = (XT)sum;
+}
+
 }  // namespace maest
 
 using namespace maest;
@@ -317,6 +406,41 @@ extern "C" int maest_patch_im2col(const void* x, int x_dtype, int B, int F, int 
                                   const int32_t* tok_ft, int P, const int32_t* t_stripes, int n_t,
                                   const int32_t* f_stripes, int n_f, void* out, int dtype, void* stream) {
     return maest_patch_im2col_strided(x, x_dtype, B, F, T, PE_S, PE_S, perm, lam, tok_ft, P, t_stripes, n_t, f_stripes, n_f, out, dtype, stream);
+}
+
+extern "C" int maest_patch_im2col_bwd(const void* dcols, int dtype, int B, int F, int T, int stride_f, int stride_t,
+                                      const int32_t* perm, const float* lam, const int32_t* tok_ft, int P,
+                                      const int32_t* t_stripes, int n_t, const int32_t* f_stripes, int n_f, int32_t* work,
+                                      int64_t work_elems, void* dx, int dx_dtype, void* stream) {
+    MAEST_REQUIRE(dcols && dx && tok_ft && work, "maest_patch_im2col_bwd: null pointer");
+    MAEST_REQUIRE(B > 0 && P > 0, "maest_patch_im2col_bwd: bad shape B=%d P=%d", B, P);
+    MAEST_REQUIRE(F >= PE_K && T >= PE_K, "maest_patch_im2col_bwd: input %dx%d smaller than a patch", F, T);
+    MAEST_REQUIRE(stride_f > 0 && stride_t > 0, "maest_patch_im2col_bwd: bad patch stride (%d, %d)", stride_f, stride_t);
+    MAEST_REQUIRE((int64_t)F * T < (1ll << 31), "maest_patch_im2col_bwd: clip of %dx%d samples too large", F, T);
+    MAEST_REQUIRE((perm == nullptr) == (lam == nullptr), "maest_patch_im2col_bwd: perm and lam go together");
+    MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16, "maest_patch_im2col_bwd: bad dtype");
+    MAEST_REQUIRE(dx_dtype == MAEST_F32 || dx_dtype == MAEST_F16, "maest_patch_im2col_bwd: dx must be fp32 or fp16");
+    MAEST_REQUIRE(n_t >= 0 && n_f >= 0 && (n_t == 0 || t_stripes) && (n_f == 0 || f_stripes),
+                  "maest_patch_im2col_bwd: bad stripe lists");
+    const int Fp = (F - PE_K) / stride_f + 1, Tp = (T - PE_K) / stride_t + 1;
+    const int64_t need = (int64_t)Fp * Tp + (lam ? 2 * (int64_t)B + 1 : 0);
+    MAEST_REQUIRE(work_elems >= need, "maest_patch_im2col_bwd: workspace of %lld int32, needs %lld", (long long)work_elems,
+                  (long long)need);
+    int32_t* lut = work;
+    int32_t* moff = lam ? work + (int64_t)Fp * Tp : nullptr;
+    int32_t* mlist = lam ? moff + B + 1 : nullptr;
+    hipLaunchKernelGGL(col2im_prep_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, tok_ft, P, Fp, Tp, perm, B, lut, moff,
+                       mlist);
+    const dim3 grid((unsigned)(((int64_t)F * T + 255) / 256), (unsigned)B);
+#define MAEST_COL2IM(GT, XT)                                                                                               \
+    hipLaunchKernelGGL((col2im_kernel<GT, XT>), grid, dim3(256), 0, (hipStream_t)stream, (const GT*)dcols, B, F, T,       \
+                       stride_f, stride_t, Fp, Tp, P, lam, lut, moff, mlist, t_stripes, n_t, f_stripes, n_f, (XT*)dx)
+    if (dtype == MAEST_BF16 && dx_dtype == MAEST_F16) MAEST_COL2IM(bf16_t, _Float16);
+    else if (dtype == MAEST_BF16) MAEST_COL2IM(bf16_t, float);
+    else if (dx_dtype == MAEST_F16) MAEST_COL2IM(float, _Float16);
+    else MAEST_COL2IM(float, float);
+#undef MAEST_COL2IM
+    return check_launch("maest_patch_im2col_bwd");
 }
 
 extern "C" int maest_token_assemble(const float* patches, const float* cls_token, const float* dist_token,

@@ -333,6 +333,28 @@ __global__ __launch_bounds__(256) void affine_kernel(float* __restrict__ x, int6
         x[i] = (x[i] + add) / div;
 }
 
+// backward of embed_pool_kernel (csrc/norm.hip): dx[b, 0] = d[b, :768], dx[b, 1] = d[b, 768:1536], dx[b, n >= 2] = d[b, 1536:] / (N - 2);
+// grid (N, B), one thread per four channels; optionally the same rows in the 16-bit operand type (the block backward's dgrad operand)
+__global__ __launch_bounds__(192) void embed_pool_bwd_kernel(const float* __restrict__ d_emb, int N, float* __restrict__ dx,
+                                                             bf16_t* __restrict__ dx_lp) {
+    const int n = blockIdx.x, b = blockIdx.y;
+    const int c = threadIdx.x * 4;
+    const float* d = d_emb + (int64_t)b * 3 * 768 + (n < 2 ? n * 768 : 2 * 768) + c;
+    float4 g = *reinterpret_cast<const float4*>(d);
+    if (n >= 2) {
+        const float cnt = (float)(N - 2);
+        g.x /= cnt; g.y /= cnt; g.z /= cnt; g.w /= cnt;
+    }
+    const int64_t o = ((int64_t)b * N + n) * 768 + c;
+    *reinterpret_cast<float4*>(dx + o) = g;
+    if (dx_lp != nullptr) {
+        chunk8 v;
+        v[0] = pack_bf2(g.x, g.y);
+        v[1] = pack_bf2(g.z, g.w);
+        *reinterpret_cast<chunk8*>(dx_lp + o) = v;
+    }
+}
+
 }  // namespace maest
 
 using namespace maest;
@@ -536,4 +558,14 @@ extern "C" int maest_scatter_head_rows(const void* src, int clips, int n_tok, in
         hipLaunchKernelGGL(scatter_head_rows_kernel<float>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                            (const float*)src, n_tok, n_head, n_pad, (float*)dst, n);
     return check_launch("maest_scatter_head_rows");
+}
+
+extern "C" int maest_embed_pool_bwd(const float* d_emb, int B, int N, float* dx, void* dx_lp, int dx_lp_dtype, void* stream) {
+    MAEST_REQUIRE(d_emb && dx, "maest_embed_pool_bwd: null pointer");
+    MAEST_REQUIRE(B > 0 && N > 2, "maest_embed_pool_bwd: bad shape B=%d N=%d", B, N);
+    MAEST_REQUIRE(dx_lp == nullptr || dx_lp_dtype == MAEST_BF16, "maest_embed_pool_bwd: the 16-bit copy must be MAEST_BF16");
+    MAEST_REQUIRE(((uintptr_t)d_emb & 15) == 0 && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dx_lp & 7) == 0,
+                  "maest_embed_pool_bwd: d_emb / dx must be 16-byte aligned, dx_lp 8-byte aligned");
+    hipLaunchKernelGGL(embed_pool_bwd_kernel, dim3(N, B), dim3(192), 0, (hipStream_t)stream, d_emb, N, dx, (bf16_t*)dx_lp);
+    return check_launch("maest_embed_pool_bwd");
 }

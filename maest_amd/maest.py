@@ -463,6 +463,9 @@ class _Engine:
             ctx["cols"] = cols
             ctx["blocks"] = []
             ctx["qs"] = qs
+            # what the input gradient (patch_im2col_bwd) needs: the forward's own operand-load options
+            ctx.update(stop_block=stop_block, self_attention=bool(return_self_attention), x_shape=tuple(x3.shape), x_dtype=x3.dtype,
+                       perm=perm, lam=lam, stripes=stripes, stride=tuple(m.patch_embed.stride))
         nblocks = len(m.blocks) if stop_block < 0 else stop_block + 1
         # bf16 perf mode: the proj / fc2 GEMMs emit their output (bias included) in bf16 and the residual add rides in
         # the LayerNorm that follows (ops.add_layernorm_fwd) -- the fp32 stream is read and rewritten by a streaming
@@ -503,7 +506,10 @@ class _Engine:
             if i == stop_block and return_self_attention:
                 # Block.forward(..., return_self_attention=True) returns attn(norm1(x)) (maest.py:414-416)
                 a = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=torch.float32)
-                return ops.embed_pool(a.reshape(B, N, EMBED_DIM)), None
+                if save:      # (the backward of this block starts at the proj GEMM: norm2 / MLP are not part of the output)
+                    ctx["blocks"].append(dict(x=x_full, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, ao=ao, lse=lse, tail=False,
+                                              ao_full=ao_full, q_rows=None))
+                return ops.embed_pool(a.reshape(B, N, EMBED_DIM)), ctx
             if split_add:
                 d1 = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=dt)
                 r = ops.add_layernorm_fwd(x, d1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save_stats=save)
@@ -541,7 +547,7 @@ class _Engine:
                                 epi=ops.EPI_RESIDUAL, aux_in=x1)
         xb = x.reshape(B, -1, EMBED_DIM)          # [B, N, 768], or [B, 2, 768] behind a restricted last block
         if stop_block >= 0:
-            return ops.embed_pool(xb), None
+            return ops.embed_pool(xb), ctx
         r = ops.head_pool_fwd(xb, m.norm.weight, m.norm.bias, m.norm.eps, save_stats=save)
         cls, dist, feat = r[:3]
         hn, hw = m.head[0], m.head[1]
@@ -575,14 +581,19 @@ class _Engine:
         else:
             with self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs):
                 G = self._backward(ctx, grads_out, sink)
-        self._step_done(ctx["x_final"].device)
+        self._step_done(ctx["cols"].device)
         return G
 
     def _backward(self, ctx, grads_out, sink=None):
         """grads_out: gradients w.r.t. the forward outputs (same tuple structure, entries may be None).
-        Returns {parameter name: fp32 gradient}.  With a `sink` (maest_amd.dist.GradReducer) every
+        Returns {parameter name: fp32 gradient}, plus "_input": the gradient w.r.t. the forward's input x3 when
+        ctx["want_dx"] asks for it.  With a `sink` (maest_amd.dist.GradReducer) every
         gradient is written straight into the sink's flat bucket view and reported as soon as it is
-        complete, so the RCCL all-reduce of a bucket overlaps with the rest of the backward."""
+        complete, so the RCCL all-reduce of a bucket overlaps with the rest of the backward.
+        A forward truncated at block k (ctx["stop_block"] = k: model(x, transformer_block=k)) starts from the backward of its
+        embedding pool and runs the blocks k .. 0 and the embeddings only; parameters it does not reach get no gradient (with a
+        sink: they are reported complete with their zeroed buffers, like DDP's find_unused_parameters=True).  Parameters that do
+        not require grad get none either, and their weight-gradient GEMMs are not run."""
         m, W = self.m, (self.w_f16 if ctx.get("f16") else self.w)
         x3m = ctx["x3m"]
         qs = ctx["qs"]
@@ -590,8 +601,12 @@ class _Engine:
         dt, B, N = ctx["dt"], ctx["B"], ctx["N"]
         Fp = m.freq_new_pos_embed.shape[2]
         M = B * N
-        dev = ctx["x_final"].device
+        dev = ctx["cols"].device
         G = {}
+        req = {n: p.requires_grad for n, p in m.named_parameters()}
+        stop = ctx.get("stop_block", -1)
+        first = len(m.blocks) - 1 if stop < 0 else stop     # the last block this backward runs
+        attn_only = stop >= 0 and ctx.get("self_attention", False)      # ... of which only the attention branch
 
         # without a sink, all parameter gradients of this pass are views of ONE zero-filled flat buffer (one fill
         # kernel instead of ~160; the wgrad kernels accumulate into it with split-K atomics)
@@ -616,6 +631,8 @@ class _Engine:
         main = torch.cuda.current_stream(dev) if side is not None else None
 
         def done(name, g):
+            if not req.get(name, True):
+                return               # frozen: its buffer may hold partial sums of a fused kernel, never reported as a gradient
             G[name] = g
             if sink is not None:
                 b = sink.note_grad(name)          # host-side count; a bucket index when its last gradient has landed
@@ -641,6 +658,8 @@ class _Engine:
             wg_w = min(wg_w if wg_w > 0 else 256, 256 - self.wgrad_reserve_cus)
 
         def wgrad(name_w, name_b, dy, x, n_out, k_out, w_shape=None):
+            if not (req.get(name_w, True) or req.get(name_b, True)):
+                return
             gw, gb = buf(name_w, n_out, k_out), buf(name_b, n_out)
             if side is not None:
                 ev = torch.cuda.Event()
@@ -655,65 +674,90 @@ class _Engine:
             done(name_w, gw if w_shape is None else gw.view(w_shape))
             done(name_b, gb)
 
-        C = m.head[1].out_features
-        cpad = ops.round_up(C, 64)
-        hn, hw = m.head[0], m.head[1]
-
-        def head_linear_bwd(dlogits, inp_lp, lin, prefix, out_dtype):
-            dl = ops.cast_rows(dlogits, dt, cpad)     # fp32 [B, C] -> operand dtype [B, cpad], zero padded (K of the dgrad GEMM)
-            wgrad(prefix + ".weight", prefix + ".bias", dl, inp_lp, C, EMBED_DIM)
-            wt = W.get(lin.weight, dt, transposed=True, pad_cols_to=64)          # [768, cpad]
-            return gemm_nt(dl, wt, None, out_dtype=out_dtype, M=B, N=EMBED_DIM, K=cpad)
-
-        d_cls = d_dist = None
-        g_h0w, g_h0b = buf("head.0.weight", EMBED_DIM), buf("head.0.bias", EMBED_DIM)
-        if m.distilled_type == "mean":
-            dlogits, dfeat_out = grads_out
-            dfeat = None
-            if dlogits is not None:
-                dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
-                dres = None if dfeat_out is None else dfeat_out.contiguous()
-                dfeat, _ = ops.layernorm_bwd(dhl, ctx["feat"], hn.weight, ctx["hmean"], ctx["hrstd"], dres,
-                                             g_h0w, g_h0b)
-            elif dfeat_out is not None:
-                dfeat = dfeat_out.contiguous()
+        if stop >= 0:
+            # truncated forward: the head, the final norm and the blocks above `stop` never ran -- nothing of theirs runs here
+            if sink is not None:
+                reached = {"cls_token", "dist_token", "new_pos_embed", "freq_new_pos_embed", "time_new_pos_embed",
+                           "patch_embed.proj.weight", "patch_embed.proj.bias"}
+                for n in req:
+                    if n.startswith("blocks."):
+                        i, rest = n.split(".", 2)[1:]
+                        if int(i) < stop or (int(i) == stop and (not attn_only or rest.startswith(("norm1.", "attn.")))):
+                            reached.add(n)
+                for n, p in m.named_parameters():
+                    if n not in reached:
+                        done(n, buf(n, *p.shape))       # its zeroed bucket view: the bucket still completes and is reduced
+            d_emb = grads_out[0] if isinstance(grads_out, (tuple, list)) else grads_out
+            if d_emb is None:
+                d_emb = torch.zeros((B, 3 * EMBED_DIM), dtype=torch.float32, device=dev)
+            dx, dx_lp = ops.embed_pool_bwd(d_emb.float().contiguous(), N, lp_dtype=dt)
         else:
-            dlogits, dlogits_d, dfeat_out = grads_out
-            dfeat = None if dfeat_out is None else dfeat_out.contiguous()
-            if dlogits is not None:
-                dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
-                d_cls, _ = ops.layernorm_bwd(dhl, ctx["cls"], hn.weight, ctx["hmean"], ctx["hrstd"], None,
-                                             g_h0w, g_h0b)
-            if dlogits_d is not None:
-                # head_dist is a bare Linear: its input gradient feeds head_pool_bwd directly, in fp32
-                d_dist = head_linear_bwd(dlogits_d.contiguous(), ctx["dist_lp"], m.head_dist, "head_dist", torch.float32)
-        done("head.0.weight", g_h0w)
-        done("head.0.bias", g_h0b)
-        g_nw, g_nb = buf("norm.weight", EMBED_DIM), buf("norm.bias", EMBED_DIM)
-        dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"],
-                               g_nw, g_nb).reshape(-1, EMBED_DIM)
-        done("norm.weight", g_nw)
-        done("norm.bias", g_nb)
-        dx_lp = dx if dt == torch.float32 else ops.cast_weights(dx, dt)[0]
+            C = m.head[1].out_features
+            cpad = ops.round_up(C, 64)
+            hn, hw = m.head[0], m.head[1]
 
-        for i in reversed(range(len(m.blocks))):
+            def head_linear_bwd(dlogits, inp_lp, lin, prefix, out_dtype):
+                dl = ops.cast_rows(dlogits, dt, cpad)     # fp32 [B, C] -> operand dtype [B, cpad], zero padded (K of the dgrad GEMM)
+                wgrad(prefix + ".weight", prefix + ".bias", dl, inp_lp, C, EMBED_DIM)
+                wt = W.get(lin.weight, dt, transposed=True, pad_cols_to=64)          # [768, cpad]
+                return gemm_nt(dl, wt, None, out_dtype=out_dtype, M=B, N=EMBED_DIM, K=cpad)
+
+            d_cls = d_dist = None
+            g_h0w, g_h0b = buf("head.0.weight", EMBED_DIM), buf("head.0.bias", EMBED_DIM)
+            if m.distilled_type == "mean":
+                dlogits, dfeat_out = grads_out
+                dfeat = None
+                if dlogits is not None:
+                    dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
+                    dres = None if dfeat_out is None else dfeat_out.contiguous()
+                    dfeat, _ = ops.layernorm_bwd(dhl, ctx["feat"], hn.weight, ctx["hmean"], ctx["hrstd"], dres,
+                                                 g_h0w, g_h0b)
+                elif dfeat_out is not None:
+                    dfeat = dfeat_out.contiguous()
+            else:
+                dlogits, dlogits_d, dfeat_out = grads_out
+                dfeat = None if dfeat_out is None else dfeat_out.contiguous()
+                if dlogits is not None:
+                    dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
+                    d_cls, _ = ops.layernorm_bwd(dhl, ctx["cls"], hn.weight, ctx["hmean"], ctx["hrstd"], None,
+                                                 g_h0w, g_h0b)
+                if dlogits_d is not None:
+                    # head_dist is a bare Linear: its input gradient feeds head_pool_bwd directly, in fp32
+                    d_dist = head_linear_bwd(dlogits_d.contiguous(), ctx["dist_lp"], m.head_dist, "head_dist", torch.float32)
+            done("head.0.weight", g_h0w)
+            done("head.0.bias", g_h0b)
+            g_nw, g_nb = buf("norm.weight", EMBED_DIM), buf("norm.bias", EMBED_DIM)
+            dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"],
+                                   g_nw, g_nb).reshape(-1, EMBED_DIM)
+            done("norm.weight", g_nw)
+            done("norm.bias", g_nb)
+            dx_lp = dx if dt == torch.float32 else ops.cast_weights(dx, dt)[0]
+        if dt == torch.float32:
+            dx_lp = dx
+
+        for i in reversed(range(first + 1)):
             blk, s = m.blocks[i], ctx["blocks"][i]
             p = f"blocks.{i}."
             H = blk.mlp.fc1.out_features
-            # fc2 (+ residual):  x2 = x1 + g W2^T + b2
-            wgrad(p + "mlp.fc2.weight", p + "mlp.fc2.bias", dx_lp, s["g"], EMBED_DIM, H)
-            dh = gemm_nt(dx_lp, W.get(blk.mlp.fc2.weight, dt, transposed=True), None, out_dtype=dt,
-                             epi=ops.EPI_MUL, aux_in=s["h"])
-            # fc1
-            wgrad(p + "mlp.fc1.weight", p + "mlp.fc1.bias", dh, s["ln2"], H, EMBED_DIM)
-            dln2 = gemm_nt(dh, W.get(blk.mlp.fc1.weight, dt, transposed=True), None, out_dtype=dt)
-            gw, gb = buf(p + "norm2.weight", EMBED_DIM), buf(p + "norm2.bias", EMBED_DIM)
-            dx1, dx1_lp = ops.layernorm_bwd(dln2, s["x1"], blk.norm2.weight, s["mean2"], s["rstd2"], dx, gw, gb,
-                                            lp_dtype=None if dt == torch.float32 else dt)
-            done(p + "norm2.weight", gw)
-            done(p + "norm2.bias", gb)
-            if dt == torch.float32:
-                dx1_lp = dx1
+            if attn_only and i == first:
+                # Block.forward(..., return_self_attention=True) = proj(attn(norm1 x)): no residual, no norm2 / MLP
+                dx1, dx1_lp, dres1 = dx, dx_lp, None
+            else:
+                # fc2 (+ residual):  x2 = x1 + g W2^T + b2
+                wgrad(p + "mlp.fc2.weight", p + "mlp.fc2.bias", dx_lp, s["g"], EMBED_DIM, H)
+                dh = gemm_nt(dx_lp, W.get(blk.mlp.fc2.weight, dt, transposed=True), None, out_dtype=dt,
+                                 epi=ops.EPI_MUL, aux_in=s["h"])
+                # fc1
+                wgrad(p + "mlp.fc1.weight", p + "mlp.fc1.bias", dh, s["ln2"], H, EMBED_DIM)
+                dln2 = gemm_nt(dh, W.get(blk.mlp.fc1.weight, dt, transposed=True), None, out_dtype=dt)
+                gw, gb = buf(p + "norm2.weight", EMBED_DIM), buf(p + "norm2.bias", EMBED_DIM)
+                dx1, dx1_lp = ops.layernorm_bwd(dln2, s["x1"], blk.norm2.weight, s["mean2"], s["rstd2"], dx, gw, gb,
+                                                lp_dtype=None if dt == torch.float32 else dt)
+                done(p + "norm2.weight", gw)
+                done(p + "norm2.bias", gb)
+                if dt == torch.float32:
+                    dx1_lp = dx1
+                dres1 = dx1
             # proj (+ residual)
             wgrad(p + "attn.proj.weight", p + "attn.proj.bias", dx1_lp, s["ao"], EMBED_DIM, EMBED_DIM)
             wt_proj = W.get(blk.attn.proj.weight, dt, transposed=True)
@@ -733,7 +777,7 @@ class _Engine:
             wgrad(p + "attn.qkv.weight", p + "attn.qkv.bias", dqkv, s["ln1"], 3 * EMBED_DIM, EMBED_DIM)
             dln1 = gemm_nt(dqkv, W.get(blk.attn.qkv.weight, dt, transposed=True), None, out_dtype=dt)
             gw, gb = buf(p + "norm1.weight", EMBED_DIM), buf(p + "norm1.bias", EMBED_DIM)
-            dx, dx_lp = ops.layernorm_bwd(dln1, s["x"], blk.norm1.weight, s["mean1"], s["rstd1"], dx1, gw, gb,
+            dx, dx_lp = ops.layernorm_bwd(dln1, s["x"], blk.norm1.weight, s["mean1"], s["rstd1"], dres1, gw, gb,
                                           lp_dtype=None if dt == torch.float32 else dt,
                                           head_tokens=(N, HEAD_TOKENS) if s["tail"] else None)
             done(p + "norm1.weight", gw)
@@ -755,6 +799,13 @@ class _Engine:
         done("time_new_pos_embed", d_tp.view(1, EMBED_DIM, 1, Tt))
         wgrad("patch_embed.proj.weight", "patch_embed.proj.bias", dpatch, ctx["cols"], EMBED_DIM, PATCH * PATCH,
               w_shape=m.patch_embed.proj.weight.shape)
+        if ctx.get("want_dx"):
+            # d x3 = col2im(dpatch W_patch): the [B*P, 768] x [768, 256] dgrad GEMM, then the gather back onto the mel samples
+            # through the forward's own stride / kept tokens / SpecMasking stripes / mixup (csrc/embed.hip: col2im_kernel)
+            dcols = gemm_nt(dpatch, W.get(m.patch_embed.proj.weight, dt, transposed=True), None, out_dtype=dt)
+            t_str, f_str = ctx["stripes"] if ctx["stripes"] is not None else (None, None)
+            G["_input"] = ops.patch_im2col_bwd(dcols, ctx["x_shape"], ctx["x_dtype"], ctx["tok_ft"], perm=ctx["perm"], lam=ctx["lam"],
+                                               t_stripes=t_str, f_stripes=f_str, stride=ctx["stride"])
         if side is not None:
             main.wait_stream(side)        # gradients are complete before backward returns to autograd / the optimizer
         return G
@@ -767,7 +818,9 @@ class _GraphLease:
 
 
 class _MaestFn(torch.autograd.Function):
-    """The single autograd edge: forward = _Engine.forward(save=True); backward = _Engine.backward."""
+    """The single autograd edge: forward = _Engine.forward(save=True); backward = _Engine.backward.  Its outputs: the forward's
+    tuple, or the one embedding tensor of a forward truncated at a block (kw["stop_block"] >= 0).  x3 gets a gradient when it
+    requires one (saliency, input attribution)."""
 
     @staticmethod
     def forward(ctx, model, x3, dt, kw, names, *params):
@@ -775,7 +828,9 @@ class _MaestFn(torch.autograd.Function):
         ctx.graph_lease = None
         if x3.is_cuda:
             model._engine.throttle()
-        if model.hip_graph and x3.is_cuda and not kw.get("f16"):      # (the captured training forward exists for the bf16 build only)
+        # (the captured training forward exists for the bf16 build only, and for the full forward of an input that needs no gradient)
+        if (model.hip_graph and x3.is_cuda and not kw.get("f16") and kw.get("stop_block", -1) < 0
+                and not x3.requires_grad):
             outs, saved, ctx.graph_lease = model._graph_train_forward(x3, dt, kw)
         else:
             outs, saved = model._engine.forward(x3, dt, save=True, **kw)
@@ -789,18 +844,20 @@ class _MaestFn(torch.autograd.Function):
         if ctx.saved is None:
             raise RuntimeError("maest_amd: backward called twice (activations are released after the first pass)")
         sink = ctx.model._grad_sink
+        ctx.saved["want_dx"] = ctx.needs_input_grad[1]
         G = ctx.model._engine.backward(ctx.saved, gout, sink)
         ctx.saved = None
         ctx.graph_lease = None       # the graph's static activation buffers may be rewritten again
+        dx = G.pop("_input", None)
         if sink is not None:   # the sink (maest_amd.dist.GradReducer) installs param.grad itself
-            return (None, None, None, None, None, *([None] * len(ctx.names)))
+            return (None, dx, None, None, None, *([None] * len(ctx.names)))
         grads = []
         for n, p in zip(ctx.names, ctx.model._param_list):
             g = G.get(n)
             if g is not None and g.shape != p.shape:
                 g = g.reshape(p.shape)
             grads.append(g)
-        return (None, None, None, None, None, *grads)
+        return (None, dx, None, None, None, *grads)
 
 
 class MAEST(nn.Module):
@@ -1069,8 +1126,9 @@ class MAEST(nn.Module):
         if x3.dtype not in (torch.float32, torch.float16):   # float16 batches (the loader's, discogs/dataset.py:58-67) go
             x3 = x3.float()                                  # straight into the patch-embedding operand load
         x3 = x3.contiguous()
-        need_grad = (transformer_block == -1 and torch.is_grad_enabled()
-                     and any(p.requires_grad for p in self.parameters()))
+        # a graph is recorded when grad mode is on and a parameter or the input requires grad -- for the full forward and for the
+        # embedding of block k alike (the reference's forward_features is ordinary autograd, models/maest.py:808-829)
+        need_grad = torch.is_grad_enabled() and (x3.requires_grad or any(p.requires_grad for p in self.parameters()))
         if need_grad and not self.training and self.precision in ("fp16", "float16", "half"):
             need_grad = False     # precision="fp16": eval() forwards record no graph even outside no_grad (a backward through them fails loudly
                                   # on outputs that do not require grad); a train() forward records in half and wants a scaled loss (_resolve_precision)
@@ -1107,17 +1165,20 @@ class MAEST(nn.Module):
         if mode == "fp16":
             kw["f16"] = True
 
+        if need_grad and self._param_names is None:
+            named = list(self.named_parameters())
+            self._param_names = [n for n, _ in named]
+            self._param_list = [p for _, p in named]
         if transformer_block != -1:
+            if need_grad:
+                kw.update(stop_block=transformer_block, return_self_attention=return_self_attention)
+                return None, _MaestFn.apply(self, x3, dt, kw, self._param_names, *self._param_list)
             with torch.no_grad():
                 emb, _ = self._engine.forward(x3, dt, stop_block=transformer_block,
                                               return_self_attention=return_self_attention, **kw)
             return None, emb
 
         if need_grad:
-            if self._param_names is None:
-                named = list(self.named_parameters())
-                self._param_names = [n for n, _ in named]
-                self._param_list = [p for _, p in named]
             outs = _MaestFn.apply(self, x3, dt, kw, self._param_names, *self._param_list)
         else:
             with torch.no_grad():

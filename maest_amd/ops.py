@@ -383,6 +383,28 @@ def patch_im2col(x: torch.Tensor, tok_ft: torch.Tensor, dtype, perm=None, lam=No
     return out
 
 
+def patch_im2col_bwd(dcols: torch.Tensor, x_shape, x_dtype, tok_ft: torch.Tensor, perm=None, lam=None, t_stripes=None, f_stripes=None,
+                     stride=(10, 10)):
+    """Input gradient of patch_im2col: dcols [B*P, 256] (fp32 / the 16-bit operand type) -> dx [B, F, T] in x_dtype (fp32 or fp16,
+    what the forward read).  The other arguments are the forward's.  Deterministic (a gather per sample, no atomics); the token
+    lookup and the mixup partner lists are built on the device in an int32 workspace."""
+    _chk(dcols, tok_ft, perm, lam, t_stripes, f_stripes)
+    assert x_dtype in (torch.float32, torch.float16) and dcols.dtype in DT and tok_ft.dtype == torch.int32
+    B, F, T = (int(v) for v in x_shape)
+    P = tok_ft.shape[0]
+    assert dcols.shape == (B * P, 256)
+    n_t = 0 if t_stripes is None else int(t_stripes.shape[1])
+    n_f = 0 if f_stripes is None else int(f_stripes.shape[1])
+    Fp, Tp = (F - 16) // int(stride[0]) + 1, (T - 16) // int(stride[1]) + 1
+    n_work = Fp * Tp + (2 * B + 1 if lam is not None else 0)
+    work = torch.empty(n_work, dtype=torch.int32, device=dcols.device)
+    dx = torch.empty((B, F, T), dtype=x_dtype, device=dcols.device)
+    call("maest_patch_im2col_bwd", _p(dcols), DT[dcols.dtype], B, F, T, int(stride[0]), int(stride[1]), _p(perm), _p(lam), _p(tok_ft), P,
+         _p(t_stripes) if n_t else None, n_t, _p(f_stripes) if n_f else None, n_f, _p(work), n_work, _p(dx),
+         F16 if x_dtype == torch.float16 else F32, _s(dcols))
+    return dx
+
+
 def token_assemble(patches, cls_token, dist_token, new_pos, freq_pos, time_pos, toffset, tok_ft, B):
     _chk(patches, cls_token, dist_token, new_pos, freq_pos, time_pos, tok_ft)
     Tt, Fg, P = time_pos.shape[-1], freq_pos.shape[-1], tok_ft.shape[0]
@@ -431,6 +453,18 @@ def embed_pool(x: torch.Tensor):
     emb = torch.empty((B, 3 * EMBED), dtype=torch.float32, device=x.device)
     call("maest_embed_pool", _p(x), B, N, _p(emb), _s(x))
     return emb
+
+
+def embed_pool_bwd(d_emb: torch.Tensor, N: int, lp_dtype=None):
+    """Backward of embed_pool: d_emb fp32 [B, 2304] -> dx fp32 [B * N, 768] (and, with lp_dtype = torch.bfloat16, the same rows
+    in the 16-bit operand type: (dx, dx_lp), like layernorm_bwd)."""
+    _chk(d_emb)
+    assert d_emb.dtype == torch.float32 and d_emb.dim() == 2 and d_emb.shape[1] == 3 * EMBED
+    B = d_emb.shape[0]
+    dx = torch.empty((B * N, EMBED), dtype=torch.float32, device=d_emb.device)
+    lp = None if lp_dtype in (None, torch.float32) else torch.empty((B * N, EMBED), dtype=lp_dtype, device=d_emb.device)
+    call("maest_embed_pool_bwd", _p(d_emb), B, N, _p(dx), _p(lp), BF16, _s(d_emb))
+    return (dx, lp) if lp_dtype is not None else dx
 
 
 def bce_logits(z, y, weight=1.0, perm=None, lam=None, loss=None, want_grad=True):
