@@ -352,6 +352,16 @@ int maest_spec_mask(float* x, int B, int F, int T, const int32_t* t_stripes, int
 int maest_logmel(const float* wave, int B, int S, const float* window, const float* twiddle,
                  const int32_t* fb_start, const int32_t* fb_len, const float* fb_w, int fb_stride,
                  float log_scale, float norm_mean, float norm_2std, float* out, void* stream);
+/* Backward of maest_logmel (added within ABI version 9: a new entry, no existing one changes).
+ * grad_out: fp32 [B, 96, T] = dL/dout; dwave: fp32 [B, S] = dL/dwave (written, not accumulated).  The forward's arguments as there;
+ * bin_band: int32 [257, 2] and bin_w: fp32 [257, 2] = the transpose of the filterbank: the (at most two) bands of each FFT bin and
+ * their weights (an unused slot: band 0, weight 0).  norm_mean does not enter the gradient.  work: fp32 scratch of
+ * work_elems >= B * T * 512 floats (the windowed gradient of every frame before overlap-add).  Deterministic: every dwave sample is
+ * summed by one thread in a fixed order, reflect folds included; the spectrum is recomputed from wave. */
+int maest_logmel_bwd(const float* wave, const float* grad_out, int B, int S, const float* window, const float* twiddle,
+                     const int32_t* fb_start, const int32_t* fb_len, const float* fb_w, int fb_stride,
+                     const int32_t* bin_band, const float* bin_w, float log_scale, float norm_mean, float norm_2std,
+                     float* work, int64_t work_elems, float* dwave, void* stream);
 
 /* ---- second mel parameterisation: AugmentMelSTFT (models/preprocess.py:17-128; north_star names the file, the
  * reference's MAEST path never calls it).  wave: fp32 [B, S] at 32 kHz; out: fp32 [B, n_mels, T], T = 1 + (S-1)/320.

@@ -383,6 +383,264 @@ __global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict_
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Backward of logmel_kernel: dwave from g = dL/dout.  Per frame t (fp32 throughout; X = the frame's one-sided spectrum, recomputed here
+// rather than saved: it is as large as the waveform):
+//   dmel[m] = g[m] log_scale / (ln 10 norm_2std (1 + log_scale mel[m]))         (1 + s mel >= 1: bounded)
+//   dP[k]   = sum_m fb[k, m] dmel[m]                                            (a bin lies in <= 2 bands: per-bin table, no scatter)
+//   dz[n]   = sum_{k=0}^{256} 2 dP[k] Re(X[k] exp(+2 pi i k n / 512))           = the real inverse DFT of the Hermitian H with
+//             H[k] = dP[k] X[k] (k = 1 .. 255), H[0] = 2 dP[0] X[0], H[256] = 2 dP[256] X[256]  (bins 0 and 256 have no mirror)
+//   dframe[n] = win[n] dz[n]
+// then overlap-add at hop 256 with the reflect padding folded back.  Two kernels: logmel_bwd_frames_kernel writes
+// dframe for every frame to an fp32 scratch [B, T, 512]; logmel_bwd_gather_kernel gives each sample ONE thread that adds its (at most
+// four) contributions in a fixed order -- deterministic, no atomics.
+//
+// The inverse transform is the forward one run backwards: with Hc = conj H and its mirror partner taken by the forward unpack's lane
+// moves, the unpack expression yields conj(Zi[k]), Zi[k] = (H[k] + conj H[256 - k]) + i (H[k] - conj H[256 - k]) exp(+2 pi i k / 512)
+// (k = 0 pairs with H[256]); the same 256-point DFT of conj(Zi) is conj(x_even + i x_odd).
+
+// the group's 256-point DFT: v[n1] = z[16 n1 + l] in, Z[l + 16 k2] at v[k2] out (plain slot order); xf: the group's exchange tile.  The
+// exchange tile (and whatever shares the wave's LDS with it) is free again on return.
+__device__ __forceinline__ void mel_fft256(cplx (&v)[16], char* xf, const float* tw256, int l) {
+    cplx tw[15];
+#pragma unroll
+    for (int k1 = 1; k1 < 16; ++k1) tw[k1 - 1] = *reinterpret_cast<const cplx*>(tw256 + 2 * (16 * k1 + l));      // W256^(l k1)
+    dft16(v);
+    *reinterpret_cast<cplx*>(xf + l * 8) = v[rev16(0)];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+        cplx ta[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) ta[i] = cmul_a<false>(v[rev16(1 + 5 * g + i)], tw[5 * g + i]);
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+            *reinterpret_cast<cplx*>(xf + (1 + 5 * g + i) * MEL_XROW + l * 8) = cmul_b<false>(v[rev16(1 + 5 * g + i)], tw[5 * g + i], ta[i]);
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const f32x4_t q = *reinterpret_cast<const f32x4_t*>(xf + l * MEL_XROW + j * 16);
+        v[2 * j] = cplx{q[0], q[1]};
+        v[2 * j + 1] = cplx{q[2], q[3]};
+    }
+    dft16(v);
+    cplx o[16];
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) o[k2] = v[rev16(k2)];
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) v[k2] = o[k2];
+    wave_lds_sync();
+}
+
+// pz[k2] = the value at slot 256 - k of the group, k = l + 16 k2: lane (16 - l) mod 16, slot 15 - k2 (lane 0: its own slot (16 - k2) mod 16;
+// for k = 0 that is slot 0 itself, which the caller replaces where 256 is meant) -- the forward unpack's lane moves
+__device__ __forceinline__ void mel_mirror_partners(const cplx (&z)[16], cplx (&pz)[16], int lane) {
+    const int l = lane & 15;
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {
+        float sr[8], si[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int k2 = 8 * hf + i;
+            const cplx za = z[(16 - k2) & 15], zb = z[15 - k2];
+            sr[i] = l == 0 ? MEL_RE(za) : MEL_RE(zb);
+            si[i] = l == 0 ? MEL_IM(za) : MEL_IM(zb);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { sr[i] = mel_row_next(sr[i], lane); si[i] = mel_row_next(si[i], lane); }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) pz[8 * hf + i] = cplx{mel_row_mirror(sr[i], lane), mel_row_mirror(si[i], lane)};
+    }
+}
+
+// out[k2] = (z + conj pz) - i (z - conj pz) wu  per slot: 2 X[k] from Z (forward), conj(Zi[k]) from conj H (backward)
+__device__ __forceinline__ void mel_unpack(const cplx (&z)[16], const cplx (&pz)[16], const float* tw512, int l, cplx (&out)[16]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        cplx e[4], d[4], t[4], wu[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wu[i] = *reinterpret_cast<const cplx*>(tw512 + 2 * (l + 16 * (4 * g + i)));      // exp(-2 pi i k / 512)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { e[i] = cadd_conj(z[4 * g + i], pz[4 * g + i]); d[i] = csub_conj(z[4 * g + i], pz[4 * g + i]); }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) t[i] = cmul_a<false>(d[i], wu[i]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i] = cmul_b<false>(d[i], wu[i], t[i]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[4 * g + i] = cadd_rot(e[i], d[i]);
+    }
+}
+
+constexpr int MELB_DMEL_OFF = 4 * MEL_PWBINS * 4;       // per wave: dmel [96 bands][4 frames] behind the power spectra (bytes)
+static_assert(MELB_DMEL_OFF + MEL_BANDS * 16 <= 4 * MEL_XFRAME, "logmel_bwd: the wave's LDS");
+
+// A wave takes four frames at a time (16 lanes per frame, as the forward); a block 64 frames of one clip.
+__global__ __launch_bounds__(256, 2) void logmel_bwd_frames_kernel(const float* __restrict__ wave_in, int S, int T,
+                                                                const float* __restrict__ window,
+                                                                const float* __restrict__ twiddle,
+                                                                const int32_t* __restrict__ fb_start,
+                                                                const int32_t* __restrict__ fb_len,
+                                                                const float* __restrict__ fb_w, int fb_stride,
+                                                                const int32_t* __restrict__ bin_band,   // [257][2]
+                                                                const float* __restrict__ bin_w,        // [257][2]
+                                                                const float* __restrict__ grad_out,     // [B, 96, T]
+                                                                float log_scale, float norm_2std,
+                                                                float* __restrict__ dframes) {          // [B, T, 512]
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int l = lane & 15, grp = lane >> 4;
+    float* wtab = reinterpret_cast<float*>(smem);                     // [512] Hann window
+    float* tw256 = wtab + 512;                                        // [16 k1][16 l][2] exp(-2 pi i l k1 / 256)
+    float* tw512 = tw256 + 512;                                       // [256][2] exp(-2 pi i k / 512)
+    int32_t* bband = reinterpret_cast<int32_t*>(tw512 + 512);         // [257][2] the bands of each bin (4 * band: float offsets into dmel)
+    float* bwt = tw512 + 512 + 2 * 260;                               // [257][2] their weights
+    char* xch = reinterpret_cast<char*>(bwt + 2 * 260) + wv * 4 * MEL_XFRAME;
+    float* pw = reinterpret_cast<float*>(xch);                        // [272 bins][4 frames]
+    f32x4_t* dml = reinterpret_cast<f32x4_t*>(xch + MELB_DMEL_OFF);    // [96 bands][4 frames]
+    const int b = blockIdx.y;
+    const int t0 = blockIdx.x * MEL_FRAMES_PER_BLOCK;
+    const float* wsrc = wave_in + (int64_t)b * S;
+    const float* gsrc = grad_out + (int64_t)b * MEL_BANDS * T;
+    const bool interior = t0 > 0 && (t0 + MEL_FRAMES_PER_BLOCK) * MEL_HOP + MEL_NFFT / 2 <= S && t0 + MEL_FRAMES_PER_BLOCK <= T &&
+                          (reinterpret_cast<uintptr_t>(wsrc) & 7) == 0;      // block-uniform
+    const int mbnd = 64 + (lane >> 1);
+    const int sa = fb_start[lane], na = fb_len[lane] < fb_stride ? fb_len[lane] : fb_stride;
+    const int sb = fb_start[mbnd] + 8 * (lane & 1), nb = fb_len[mbnd] < fb_stride ? fb_len[mbnd] : fb_stride;
+    const float ls4 = 0.25f * log_scale;
+    const float dcoef = log_scale / (2.30258509299404568f * norm_2std);     // d out / d mel = dcoef / (1 + s mel)
+    if (threadIdx.x < 128) *reinterpret_cast<f32x4_t*>(wtab + 4 * threadIdx.x) = *reinterpret_cast<const f32x4_t*>(window + 4 * threadIdx.x);
+    else *reinterpret_cast<f32x4_t*>(tw512 + 4 * (threadIdx.x - 128)) = *reinterpret_cast<const f32x4_t*>(twiddle + 4 * (threadIdx.x - 128));
+    *reinterpret_cast<cplx*>(tw256 + 2 * threadIdx.x) =
+        *reinterpret_cast<const cplx*>(twiddle + 4 * (((threadIdx.x & 15) * (threadIdx.x >> 4)) & 255));
+    for (int i = threadIdx.x; i < 2 * MEL_NBINS; i += 256) {
+        bband[i] = 4 * bin_band[i];
+        bwt[i] = bin_w[i];
+    }
+    float wa[8], wb[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        wa[i] = i < na ? fb_w[lane * fb_stride + i] : 0.0f;
+        wb[i] = 8 * (lane & 1) + i < nb ? fb_w[mbnd * fb_stride + 8 * (lane & 1) + i] : 0.0f;
+    }
+    __syncthreads();
+
+    auto frames = [&](auto interior_tag) {
+        constexpr bool INTERIOR = decltype(interior_tag)::value;
+        for (int quad = 0; quad < 4; ++quad) {
+            const int tl0 = wv * 16 + quad * 4;      // first of this wave's four frames within the block
+            const int t = t0 + tl0 + grp;            // this lane group's frame (>= T: clamped fetch, zero gradient, not stored)
+            // ---- the forward, recomputed: framing + window, 256-point DFT, unpack to 2 X[k] (k = l + 16 k2 at xs[k2]; 2 X[256] in lane 0)
+            cplx v[16];
+            {
+                cplx xin[16];
+                mel_fetch<INTERIOR>(xin, wsrc, t, T, S, l);
+#pragma unroll
+                for (int n1 = 0; n1 < 16; ++n1) v[n1] = xin[n1] * *reinterpret_cast<const cplx*>(wtab + 2 * (16 * n1 + l));
+            }
+            mel_fft256(v, xch + grp * MEL_XFRAME, tw256, l);
+            if (lane < 4 * (MEL_PWBINS - MEL_NBINS)) pw[4 * MEL_NBINS + lane] = 0.0f;
+            cplx xs[16];
+            float x256;
+            {
+                cplx pz[16];
+                mel_mirror_partners(v, pz, lane);
+                x256 = 2.0f * (MEL_RE(v[0]) - MEL_IM(v[0]));                 // 2 X[256] = 2 (Re Z[0] - Im Z[0])  (lane 0)
+                if (l == 0) pw[4 * 256 + grp] = x256 * x256;
+                mel_unpack(v, pz, tw512, l, xs);
+            }
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                const cplx q = csqr2(xs[k2]);
+                pw[4 * (l + 16 * k2) + grp] = MEL_RE(q) + MEL_IM(q);          // the power spectrum times four, as the forward keeps it
+            }
+            wave_lds_sync();
+            // ---- the mel bands of the four frames (the forward's projection), then dmel into LDS
+            {
+                const f32x4_t* pwq = reinterpret_cast<const f32x4_t*>(xch);
+                f32x4_t acc_a = {0.0f, 0.0f, 0.0f, 0.0f}, acc_b = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    const f32x4_t pa = pwq[sa + i], pb = pwq[sb + i];
+                    acc_a = __builtin_elementwise_fma(pa, f32x4_t{wa[i], wa[i], wa[i], wa[i]}, acc_a);
+                    acc_b = __builtin_elementwise_fma(pb, f32x4_t{wb[i], wb[i], wb[i], wb[i]}, acc_b);
+                }
+#pragma unroll 1
+                for (int i = 8; i < na; ++i) acc_a += pwq[sa + i] * fb_w[lane * fb_stride + i];
+#pragma unroll
+                for (int f = 0; f < 4; ++f) acc_b[f] += mel_lane_xor1(acc_b[f]);
+                if ((lane & 1) == 0)
+#pragma unroll 1
+                    for (int i = 16; i < nb; ++i) acc_b += pwq[sb + i] * fb_w[mbnd * fb_stride + i];
+                f32x4_t da, db;
+#pragma unroll
+                for (int f = 0; f < 4; ++f) {
+                    const int tt = t0 + tl0 + f;
+                    const float ga = tt < T ? gsrc[(int64_t)lane * T + tt] : 0.0f;
+                    const float gb = tt < T ? gsrc[(int64_t)mbnd * T + tt] : 0.0f;
+                    da[f] = ga * dcoef / __builtin_fmaf(acc_a[f], ls4, 1.0f);
+                    db[f] = gb * dcoef / __builtin_fmaf(acc_b[f], ls4, 1.0f);
+                }
+                wave_lds_sync();                      // every lane has read the power spectra (dml lies behind them: no overlap, but keep the order)
+                dml[lane] = da;
+                if ((lane & 1) == 0) dml[mbnd] = db;
+            }
+            wave_lds_sync();
+            // ---- dP per bin (at most two bands), H = dP X with the mirror-less bins doubled, conj H
+            const float* dmf = reinterpret_cast<const float*>(dml);
+            cplx hc[16];
+#pragma unroll
+            for (int k2 = 0; k2 < 16; ++k2) {
+                const int k = l + 16 * k2;
+                const float dp = bwt[2 * k] * dmf[bband[2 * k] + grp] + bwt[2 * k + 1] * dmf[bband[2 * k + 1] + grp];
+                const float c = (k2 == 0 && l == 0) ? dp : 0.5f * dp;       // H[0] = 2 dP X[0]; H[k] = dP X[k]; xs = 2 X
+                hc[k2] = cplx{c * MEL_RE(xs[k2]), -(c * MEL_IM(xs[k2]))};
+            }
+            float h256;
+            {
+                h256 = (bwt[512] * dmf[bband[512] + grp] + bwt[513] * dmf[bband[513] + grp]) * x256;
+            }
+            // ---- inverse: conj(Zi) from conj H and its mirror (k = 0 pairs with H[256]), the 256-point DFT, conj -> (even, odd) samples
+            {
+                cplx pz[16];
+                mel_mirror_partners(hc, pz, lane);
+                if (l == 0) pz[0] = cplx{h256, 0.0f};
+                mel_unpack(hc, pz, tw512, l, v);
+            }
+            wave_lds_sync();                          // dmel / the power spectra are read: the exchange tiles are free
+            mel_fft256(v, xch + grp * MEL_XFRAME, tw256, l);
+            if (t < T) {
+                float* dst = dframes + ((int64_t)b * T + t) * MEL_NFFT;
+#pragma unroll
+                for (int k2 = 0; k2 < 16; ++k2) {
+                    const int m = l + 16 * k2;        // samples 2 m, 2 m + 1 = (Re, -Im)
+                    const cplx w2 = *reinterpret_cast<const cplx*>(wtab + 2 * m);
+                    *reinterpret_cast<cplx*>(dst + 2 * m) = cplx{w2[0] * MEL_RE(v[k2]), -(w2[1] * MEL_IM(v[k2]))};
+                }
+            }
+        }
+    };
+    if (interior) frames(std::true_type{});
+    else frames(std::false_type{});
+}
+
+// Overlap-add + reflect fold: one thread per sample j of clip b, its contributions in a fixed order -- frame j / 256 (n = 256 + j mod 256),
+// frame j / 256 + 1 (n = j mod 256), the left fold (padded index -j, 1 <= j <= 256: frame 0, n = 256 - j), the right fold (padded index
+// 2 (S - 1) - j >= S: frame T - 1 only, where it reaches).
+__global__ __launch_bounds__(256) void logmel_bwd_gather_kernel(const float* __restrict__ dframes, int S, int T, float* __restrict__ dwave) {
+    const int j = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (j >= S) return;
+    const float* d = dframes + (int64_t)b * T * MEL_NFFT;
+    const int ta = j / MEL_HOP, r = j % MEL_HOP;          // ta <= (S - 1) / 256 <= T - 1
+    float acc = d[(int64_t)ta * MEL_NFFT + MEL_HOP + r];
+    if (ta + 1 < T) acc += d[(int64_t)(ta + 1) * MEL_NFFT + r];
+    if (j >= 1 && j <= MEL_NFFT / 2) acc += d[MEL_NFFT / 2 - j];
+    const int ir = 2 * (S - 1) - j;                       // >= S  <=>  j <= S - 2
+    const int last0 = (T - 1) * MEL_HOP - MEL_NFFT / 2;   // first padded index of frame T - 1
+    if (j <= S - 2 && ir - last0 < MEL_NFFT) acc += d[(int64_t)(T - 1) * MEL_NFFT + ir - last0];
+    dwave[(int64_t)b * S + j] = acc;
+}
+
 }  // namespace maest
 
 using namespace maest;
@@ -401,4 +659,26 @@ extern "C" int maest_logmel(const float* wave, int B, int S, const float* window
     hipLaunchKernelGGL(logmel_kernel, grid, dim3(256), smem_bytes, (hipStream_t)stream, wave, S, T, window, twiddle,
                        fb_start, fb_len, fb_w, fb_stride, log_scale, norm_mean, norm_2std, out);
     return check_launch("maest_logmel");
+}
+
+extern "C" int maest_logmel_bwd(const float* wave, const float* grad_out, int B, int S, const float* window, const float* twiddle,
+                                const int32_t* fb_start, const int32_t* fb_len, const float* fb_w, int fb_stride,
+                                const int32_t* bin_band, const float* bin_w, float log_scale, float norm_mean, float norm_2std,
+                                float* work, int64_t work_elems, float* dwave, void* stream) {
+    (void)norm_mean;                              // the mean shifts the output, not its gradient
+    MAEST_REQUIRE(wave && grad_out && window && twiddle && fb_start && fb_len && fb_w && bin_band && bin_w && work && dwave,
+                  "maest_logmel_bwd: null pointer");
+    MAEST_REQUIRE(B > 0 && S > MEL_NFFT / 2, "maest_logmel_bwd: bad shape B=%d S=%d (reflect padding needs S > 256)", B, S);
+    MAEST_REQUIRE(fb_stride > 0, "maest_logmel_bwd: bad fb_stride");
+    const int T = 1 + S / MEL_HOP;
+    MAEST_REQUIRE(work_elems >= (int64_t)B * T * MEL_NFFT, "maest_logmel_bwd: workspace of %lld floats, needs B * T * 512 = %lld",
+                  (long long)work_elems, (long long)B * T * MEL_NFFT);
+    const int smem_bytes = (512 + 512 + 512) * 4 + 2 * 2 * 260 * 4 + 4 * 4 * MEL_XFRAME;
+    hipLaunchKernelGGL(logmel_bwd_frames_kernel, dim3((T + MEL_FRAMES_PER_BLOCK - 1) / MEL_FRAMES_PER_BLOCK, B), dim3(256), smem_bytes,
+                       (hipStream_t)stream, wave, S, T, window, twiddle, fb_start, fb_len, fb_w, fb_stride, bin_band, bin_w, grad_out,
+                       log_scale, norm_2std, work);
+    int rc = check_launch("maest_logmel_bwd (frames)");
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(logmel_bwd_gather_kernel, dim3((S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, work, S, T, dwave);
+    return check_launch("maest_logmel_bwd (gather)");
 }

@@ -1,7 +1,8 @@
 """On-the-fly waveform -> log-mel front end, same module surface as the reference's
 ``models/helpers/melspectrogram.py:13-60`` (class constants :16-24, ``znorm`` :44-45,
 ``forward`` :47-60), with the arithmetic done by ONE fused HIP kernel (csrc/mel.hip) instead of
-torchaudio's Spectrogram + MelScale + three elementwise passes.
+torchaudio's Spectrogram + MelScale + three elementwise passes.  A waveform that requires grad (with grad mode on) goes through an
+autograd Function whose backward is a second HIP kernel pair (maest_logmel_bwd); every other call takes the plain forward.
 
 The filterbank / window / twiddle tables are computed once on the host in float64 (slaney mel scale,
 slaney area normalisation, f in [0, sr/2] -- torchaudio ``melscale_fbanks`` semantics) and shipped to
@@ -13,6 +14,7 @@ import math
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 from torch.nn import Module
 
 from . import ops
@@ -68,6 +70,14 @@ class MelConstants:
             else:
                 starts.append(int(nz[0]))
                 lens.append(int(nz[-1] - nz[0] + 1))
+        # the transpose of the bank for the backward (maest_logmel_bwd): each bin's (at most two) bands and their weights
+        bin_band = np.zeros((n_fft // 2 + 1, 2), np.int32)
+        bin_w = np.zeros((n_fft // 2 + 1, 2), np.float32)
+        for k in range(n_fft // 2 + 1):
+            nz = np.nonzero(fb[k])[0]
+            assert len(nz) <= 2, f"bin {k} lies in {len(nz)} mel bands; the backward's per-bin table holds two"
+            bin_band[k, : len(nz)] = nz
+            bin_w[k, : len(nz)] = fb[k, nz]
         self.fb_stride = max(8, int(math.ceil(max(lens) / 8) * 8))
         w = np.zeros((n_mel, self.fb_stride), np.float32)
         for m in range(n_mel):
@@ -81,9 +91,28 @@ class MelConstants:
         self.fb_start = torch.tensor(starts, dtype=torch.int32, device=device)
         self.fb_len = torch.tensor(lens, dtype=torch.int32, device=device)
         self.fb_w = torch.from_numpy(w).to(device)
+        self.bin_band = torch.from_numpy(bin_band).to(device)
+        self.bin_w = torch.from_numpy(bin_w).to(device)
         self.log_scale = float(log_scale)
         self.norm_mean = float(norm_mean)
         self.norm_2std = float(norm_std * 2)
+
+
+class _LogMelFn(torch.autograd.Function):
+    """fp32 [B, S] -> [B, 96, T] with a backward (maest_logmel_bwd).  Only the waveform is saved: the backward recomputes the
+    spectrum."""
+
+    @staticmethod
+    def forward(ctx, w, consts):
+        ctx.consts = consts
+        ctx.save_for_backward(w)
+        return ops.logmel(w, consts)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (w,) = ctx.saved_tensors
+        return ops.logmel_bwd(w, g.float().contiguous(), ctx.consts), None
 
 
 class _ConstantBuffers(Module):
@@ -143,7 +172,10 @@ class MelSpectrogram(Module):
         if w.dtype != torch.float32:
             w = w.float()
         w = w.contiguous()
-        out = ops.logmel(w, self._constants(w.device))
+        if torch.is_grad_enabled() and w.requires_grad:        # a waveform that wants a gradient (saliency, a loss behind a generator)
+            out = _LogMelFn.apply(w, self._constants(w.device))
+        else:
+            out = ops.logmel(w, self._constants(w.device))
         if squeeze:
             return out[0]
         return out.reshape(waveform.shape[:-1] + out.shape[-2:])

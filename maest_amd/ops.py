@@ -535,6 +535,22 @@ def logmel(wave: torch.Tensor, consts) -> torch.Tensor:
     return out
 
 
+def logmel_bwd(wave: torch.Tensor, grad: torch.Tensor, consts) -> torch.Tensor:
+    """Backward of logmel: wave fp32 [B, S] (the forward's input), grad fp32 [B, 96, 1 + S // 256] -> dwave fp32 [B, S].
+    Deterministic (one thread sums each sample; no atomics).  Scratch: the windowed gradient of every frame, B * T * 2 KB."""
+    _chk(wave, grad)
+    assert wave.dtype == torch.float32 and wave.dim() == 2 and grad.dtype == torch.float32
+    B, S = wave.shape
+    T = 1 + S // 256
+    assert grad.shape == (B, 96, T), (tuple(grad.shape), (B, 96, T))
+    work = torch.empty(B * T * 512, dtype=torch.float32, device=wave.device)
+    dwave = torch.empty((B, S), dtype=torch.float32, device=wave.device)
+    _timed_call("maest_logmel_bwd", 0.0, _p(wave), _p(grad), B, S, _p(consts.window), _p(consts.twiddle), _p(consts.fb_start),
+                _p(consts.fb_len), _p(consts.fb_w), consts.fb_stride, _p(consts.bin_band), _p(consts.bin_w), consts.log_scale,
+                consts.norm_mean, consts.norm_2std, _p(work), work.numel(), _p(dwave), _s(wave))
+    return dwave
+
+
 def scale_(x: torch.Tensor, alpha: float):
     _chk(x)
     assert x.dtype == torch.float32
