@@ -2,20 +2,24 @@
 """Headline benchmark of the MAEST hot path on MI355X (BASELINE.json: clips/sec, 10 s @ 16 kHz,
 96-mel, MAEST-10s fwd+bwd).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One "step" = one full training step of BASELINE config 3 on ONE batch of synthetic input already
 resident in HBM: mixup draw -> fused mixup/patchout/patch-embed -> 12-block ViT forward -> BCE ->
 hand-written backward -> (N > 1: RCCL gradient all-reduce over xGMI, overlapped) -> AdamW.
-Per-GPU batch is fixed (weak scaling); `value` is the whole-job clips/s.  Rank 0 prints ONE JSON line
-that also carries
+Per-GPU batch is fixed (weak scaling); `value` is the whole-job clips/s.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline figure needs: set up, W warm-up steps, K timed steps,
+--dump-outputs if given, the line.  --full adds everything else the benchmark measures or checks, each in
+passes of its own after the timed steps, among them
   "roofline":     the dominant kernel (bf16 MFMA GEMM) priced against the 2.5 PFLOP/s dense bf16 peak,
-                  timed live with HIP events on the launch stream inside the timed region;
+                  timed with HIP events on the launch stream in a second, serialized pass over the K steps;
   "cpu_baseline": the oracle (CPU restatement of the reference, oracle/maest_oracle.py -- proven
-                  bit-identical to the imported reference) timed on this box's host cores on a bounded
-                  sample of the same workload.  A reported baseline, not the target.
+                  bit-identical to the imported reference) timed on the host cores on a bounded
+                  sample of the same workload.  A reported baseline, not the target;
+and, on the default configuration, the other BASELINE configurations as sub-objects of the line.
 """
 import argparse
 import json
@@ -76,7 +80,7 @@ def pmc_traffic():
 def measure_pmc_traffic(timeout_s=150):
     """HBM bytes per GEMM call of the dominant kernel, MEASURED by this run: two rocprofv3 passes (--kernel-trace --pmc
     FETCH_SIZE, then WRITE_SIZE: counters in their own passes, no other trace domain) over a short child run of this same
-    file (2 steps + 1 warm-up, kernels serialized, no side cases), on this GPU.  Per call = sum over every gemm_nt256o /
+    file (a plain run: 2 steps + 1 warm-up, kernels serialized), on this GPU.  Per call = sum over every gemm_nt256o /
     gemm_nt256w launch (256-row tiles and the 128-row-tile launch behind some of them) / number of 256-row-tile launches;
     traffic = 2 x FETCH_SIZE + WRITE_SIZE (MI355X_MICROARCH.md, HBM section: FETCH_SIZE counts half of the wide coalesced
     reads on gfx950; profiles/r03c_pmc_traffic.json holds the same passes with their calibration on known byte counts:
@@ -90,8 +94,7 @@ def measure_pmc_traffic(timeout_s=150):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             with tempfile.TemporaryDirectory(prefix="maest_pmc_", dir="/tmp") as d:
                 cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "p", "--",
-                       sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                       "--no-kernel-timing", "--serial-kernels", "--no-side-cases"]
+                       sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--serial-kernels"]
                 env = dict(os.environ, TMPDIR="/tmp", MAEST_BENCH_PMC="0")
                 r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout_s)
                 if r.returncode != 0:
@@ -693,11 +696,17 @@ def main():
                     help="train: BASELINE configs[2] (the headline metric); infer: configs[1]; ts: configs[4] "
                          "(teacher-student, waveform -> HIP log-mel on the fly -> mixup -> 519-way separated heads, 30 s)")
     ap.add_argument("--hip-graph", action="store_true", help="replay the forward from a captured HIP graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures or checks: the complete-last-block figure, the "
+                         "serialized kernel pass (roofline, kernel_ms_per_step, attention set; live PMC traffic), the log-mel kernel, "
+                         "deviation_vs_fp32, the CPU baseline, at N > 1 the rank check, and on the default configuration the side cases "
+                         "and the loader.  Without it a run times the headline steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the complete-last-block "
+                                                                   "figure and live PMC traffic)")
     ap.add_argument("--cpu-batch", type=int, default=None, help="clips per oracle step of the CPU baseline (SURVEY 8d: B = 8)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: skip the serialized kernel pass and the log-mel kernel")
     ap.add_argument("--no-side-cases", action="store_true",
-                    help="skip the `infer` / `infer_parity` (configs[1]), `train30s` (configs[3] per-GPU shape) and `ts` (configs[4]) "
+                    help="--full: skip the `infer` / `infer_parity` (configs[1]), `train30s` (configs[3] per-GPU shape) and `ts` (configs[4]) "
                          "sub-objects of the default line")
     ap.add_argument("--complete-last-block", action="store_true",
                     help="evaluate the last block on every token (A/B reference for the head-token restriction)")
@@ -710,7 +719,7 @@ def main():
                          "all-reduce anyway (the data-parallel exchange path on a single GPU)")
     ap.add_argument("--with-loader", action="store_true",
                     help="add the `loader` sub-object (the on-disk mel reader alone and double-buffered against the training step) "
-                         "to a non-default line; the default line carries it anyway")
+                         "to the line; the --full default line carries it anyway")
     ap.add_argument("--ranks-share-gpu", action="store_true",
                     help="debug / test switch: every rank of a --gpus N job runs on device 0 and gloo carries the device tensors of "
                          "the gradient exchange -- the whole N-rank launch, bootstrap, bucket and timing path on a one-GPU box "
@@ -720,7 +729,7 @@ def main():
                          "and a fixed sample of the parameters and AdamW moments it updated; evaluation: the logits), for comparing builds")
     ap.add_argument("--check-ranks", action="store_true",
                     help="after the timed steps: compare the weights of all ranks (they must be bit-identical) and report the "
-                         "bucket all-reduces launched per step as `dp_check` on the line")
+                         "bucket all-reduces launched per step as `dp_check` on the line (--full does so at N > 1)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus)
@@ -753,27 +762,30 @@ def main():
     if args.dump_outputs and rank == 0:           # (before any later pass steps the model again)
         dumped = dump_outputs(case, last[0], args.dump_outputs)
     del last
+    # ---- the passes below that the headline line does not need run under --full only
+    full = args.full
 
     # ---- the same K steps with the last block evaluated on every token (N = 1 only; reported next to `value` so that the
     # effect of restricting it to the head's tokens is on the line itself)
     complete = None
-    if world == 1 and getattr(net._engine, "head_tail", False) and not args.no_cpu_baseline and not args.hip_graph:
+    if full and world == 1 and getattr(net._engine, "head_tail", False) and not args.no_cpu_baseline and not args.hip_graph:
         net._engine.head_tail = False
         complete = timed_steps(step, args.steps, 2, 1, dev)
         net._engine.head_tail = True
 
     # ---- roofline pass (rank 0, N = 1)
     timer = None
-    if not args.no_kernel_timing and world == 1:
+    if full and not args.no_kernel_timing and world == 1:
         timer = kernel_pass(case, args.steps)
 
-    # ---- data-parallel evidence on the line: per-bucket all-reduce times of the timed steps, and (always at N > 1) the rank check
+    # ---- data-parallel evidence on the line: per-bucket all-reduce times of the timed steps, and (--check-ranks, or --full at N > 1)
+    # the rank check
     dp_buckets = None
     red = getattr(net, "_grad_sink", None)
     if red is not None and red.timing:
         dp_buckets = red.bucket_times()
     dp_check = None
-    if args.check_ranks or world > 1:
+    if args.check_ranks or (full and world > 1):
         dp_check = check_ranks(net, world, dev)
 
     if rank == 0:
@@ -830,26 +842,26 @@ def main():
                                        "(cls, dist) only, forward and backward; logits, features and all gradients equal "
                                        "the complete evaluation's" if tail_on else "complete")
         if timer is not None:
-            # HBM traffic of the dominant kernel from live PMC passes: on the headline configuration of a complete default
+            # HBM traffic of the dominant kernel from live PMC passes: on the headline configuration of a --full default
             # line only (N = 1, configs[2], bf16; MAEST_BENCH_PMC=0 or --no-cpu-baseline skip it: +50 s)
             live = None
             if (world == 1 and args.mode == "train" and T <= 640 and args.precision == "bf16" and not args.no_cpu_baseline
                     and B == 256 and os.environ.get("MAEST_BENCH_PMC", "1") != "0"):
                 live = measure_pmc_traffic()
             out.update(kernel_report(case, timer, args.steps, args.precision, with_traffic=True, live_traffic=live))
-        if world == 1 and not args.no_kernel_timing:
+        if full and world == 1 and not args.no_kernel_timing:
             # the HBM-bound front end of the path: the log-mel kernel on a full batch of waveforms
             try:
                 out["mel"] = time_mel_kernel(dev, B, (T - 1) * 256)
             except Exception as e:  # pragma: no cover
                 out["mel"] = {"error": repr(e)}
-        if world == 1 and args.precision != "fp32":
+        if full and world == 1 and args.precision != "fp32":
             try:
                 out["deviation_vs_fp32"] = deviation_vs_fp32(case, args.precision)
             except Exception as e:  # pragma: no cover
                 out["deviation_vs_fp32"] = {"error": repr(e)}
-        # ---- the other single-GPU BASELINE configurations, driver-visible on the same line (default run only)
-        default_line = (world == 1 and args.mode == "train" and args.frames is None and args.batch is None
+        # ---- the other single-GPU BASELINE configurations on the same line (--full on the default configuration only)
+        default_line = (full and world == 1 and args.mode == "train" and args.frames is None and args.batch is None
                         and args.patchout is None and not args.hip_graph and not args.no_side_cases
                         and not args.complete_last_block and not args.serial_kernels and not args.force_collective
                         and not args.no_fold_delta)
@@ -902,7 +914,7 @@ def main():
                 out["loader"] = loader_case(args, dev)
             except Exception as e:  # pragma: no cover
                 out["loader"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             try:
                 cb = args.cpu_batch if args.cpu_batch is not None else (8 if T <= 640 else 2)
                 out["cpu_baseline"] = (cpu_baseline(cb, T, patchout, teacher_student=ts, waveform=ts) if train

@@ -3,10 +3,10 @@
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 TAG=${1:-r02c}; O=gpurun_out/$TAG; mkdir -p $O
-timeout 400 python bench.py --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_train_b256.json
+timeout 400 python bench.py --full --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_train_b256.json
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -o p -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --serial-kernels > $O/prof2.log 2>&1
 cp $(find $O/prof2 -name p_kernel_stats.csv | head -1) $O/${TAG}_bench_train_b256_serial_kernel_stats.csv
-timeout 300 python bench.py --mode infer --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256.json
+timeout 300 python bench.py --full --mode infer --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256.json
 head -4 $O/${TAG}_bench_train_b256_serial_kernel_stats.csv | cut -c1-150
 python -c "
 import json

@@ -4,13 +4,13 @@
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 TAG=${1:-r03a}; O=gpurun_out/$TAG; mkdir -p $O
-timeout 600 python bench.py --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_train_b256.json
-timeout 400 python bench.py --mode infer --steps 20 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256.json
-timeout 400 python bench.py --mode ts --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/${TAG}_bench_ts_b128.json
-timeout 400 python bench.py --frames 1876 --batch 128 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_train30s_b128.json
-timeout 400 python bench.py --mode infer --frames 1876 --batch 64 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_infer30s_b64.json
-timeout 400 python bench.py --mode infer --precision bf16x3 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256_bf16x3.json
-timeout 600 python bench.py --mode infer --precision fp32 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256_fp32.json
+timeout 600 python bench.py --full --steps 10 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_train_b256.json
+timeout 400 python bench.py --full --mode infer --steps 20 --warmup 3 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256.json
+timeout 400 python bench.py --full --mode ts --steps 5 --warmup 2 2>/dev/null | tail -1 > $O/${TAG}_bench_ts_b128.json
+timeout 400 python bench.py --full --frames 1876 --batch 128 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_train30s_b128.json
+timeout 400 python bench.py --full --mode infer --frames 1876 --batch 64 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_infer30s_b64.json
+timeout 400 python bench.py --full --mode infer --precision bf16x3 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256_bf16x3.json
+timeout 600 python bench.py --full --mode infer --precision fp32 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${TAG}_bench_infer_b256_fp32.json
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o p -- python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-timing --serial-kernels > $O/prof.log 2>&1
 cp $(find $O/prof -name p_kernel_stats.csv | head -1) $O/${TAG}_bench_train_b256_serial_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE; do
