@@ -362,6 +362,25 @@ int maest_logmel_bwd(const float* wave, const float* grad_out, int B, int S, con
                      const int32_t* fb_start, const int32_t* fb_len, const float* fb_w, int fb_stride,
                      const int32_t* bin_band, const float* bin_w, float log_scale, float norm_mean, float norm_2std,
                      float* work, int64_t work_elems, float* dwave, void* stream);
+/* The log-mel of maest_logmel into the on-disk mel file's layout (added within ABI version 9): a RAGGED batch of tracks packed in
+ * `wave` (fp32, total_in samples) -> IEEE half rows [frame][96] = log10(1 + log_scale mel), no z-norm, rounded to nearest even, packed
+ * in `rows` (total_rows rows, 16-byte aligned).  tracks: int64 [n_tracks][5] = {sample offset, S > 256, first frame f0, frame count n,
+ * row offset}: frames f0 .. f0 + n - 1 of the track's T = 1 + S / 256 (framing and reflect padding per track as maest_logmel) go to rows
+ * row offset .. + n - 1.  block_start: int32 [n_tracks + 1], the first block of each track (ceil(n / 64) blocks each), n_blocks = its last
+ * entry.  The device tables are not read here: an entry outside the buffers is computed on valid memory and stores nothing.  Each
+ * track's frame values are those of maest_logmel (norm_mean 0, norm_2std 1) bit for bit; a track starting on an 8-byte boundary
+ * takes the aligned fetch in its interior. */
+int maest_logmel_rows_f16(const float* wave, int64_t total_in, const int64_t* tracks, const int32_t* block_start, int n_tracks,
+                          int n_blocks, const float* window, const float* twiddle, const int32_t* fb_start, const int32_t* fb_len,
+                          const float* fb_w, int fb_stride, float log_scale, void* rows, int64_t total_rows, void* stream);
+/* Polyphase resampler, a ragged batch (added within ABI version 9): torchaudio.functional.resample's sinc_interp_hann with the rates
+ * reduced by their gcd to orig -> new_rate.  Output j = new_rate q + p of a track = sum_i taps[i][p] x[orig q + first[p] + i - width],
+ * x = the track (zero outside it).  taps: fp32 [n_taps][new_rate] (each phase's non-zero band, zero-padded to n_taps), first: int32
+ * [new_rate].  tracks: int64 [n_tracks][4] = {input offset, input length, output offset, output length}; block_start: int32
+ * [n_tracks + 1], 256 outputs per block, n_blocks = its last entry.  Entries outside the buffers store nothing. */
+int maest_resample(const float* in, int64_t total_in, const int64_t* tracks, const int32_t* block_start, int n_tracks,
+                   int n_blocks, int orig, int new_rate, int width, const float* taps, const int32_t* first, int n_taps,
+                   float* out, int64_t total_out, void* stream);
 
 /* ---- second mel parameterisation: AugmentMelSTFT (models/preprocess.py:17-128; north_star names the file, the
  * reference's MAEST path never calls it).  wave: fp32 [B, S] at 32 kHz; out: fp32 [B, n_mels, T], T = 1 + (S-1)/320.

@@ -64,6 +64,8 @@ SIGNATURES = {
     "maest_melfile_assemble": [_P, _P, _P, _I, _I, _I, _I, _F, _F, _P, _P],
     "maest_logmel": [_P, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _P, _P],
     "maest_logmel_bwd": [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _P, _L, _P, _P],
+    "maest_logmel_rows_f16": [_P, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _F, _P, _L, _P],
+    "maest_resample": [_P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _P],
     "maest_scale_f32": [_P, _L, _F, _P],
     "maest_scale_dev_f32": [_P, _L, _P, _P],
     "maest_cast_rows": [_P, _L, _P, _L, _I, _I, _I, _P],

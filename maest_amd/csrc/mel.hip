@@ -193,6 +193,82 @@ constexpr int MEL_XROW = 18 * 8;                  // exchange tile: 16 rows (k1)
 constexpr int MEL_XFRAME = 16 * MEL_XROW;         // 2304 B per frame
 constexpr int MEL_PWBINS = 272;                   // 257 bins + 15 zero bins (a 16-weight register window starting at the last band's first bin)
 
+// Where a block's [96][64] output tile goes (the only part of the block that differs between the two entries):
+//   MelEpiBandMajor -- maest_logmel: fp32 [B, 96, T], 256-byte runs along T;
+//   MelEpiRowsF16   -- maest_logmel_rows_f16: IEEE half rows [frame][96] (the on-disk mel file's layout), the block's frames one
+//                      contiguous run of up to 64 x 192 bytes, stored 16 bytes per thread.
+struct MelEpiBandMajor {
+    float* __restrict__ out;         // [B, 96, T]
+    int b = 0;                       // the block's clip
+    __device__ __forceinline__ const float* locate(const float* wave_in, int& S, int&, int& t0) {      // grid (T / 64, B)
+        b = blockIdx.y;
+        t0 = blockIdx.x * MEL_FRAMES_PER_BLOCK;
+        return wave_in + (int64_t)b * S;
+    }
+    __device__ __forceinline__ void store(const float* otile, int t0, int T) const {
+        const int tl = threadIdx.x & 63, m0 = threadIdx.x >> 6;       // thread = frame tid & 63 of bands (tid >> 6) + 4 j
+        if (t0 + tl < T) {
+            float* dst = out + ((int64_t)b * MEL_BANDS + m0) * T + t0 + tl;
+            const float* src = otile + m0 * MEL_OUT_LD + tl;
+#pragma unroll
+            for (int j = 0; j < MEL_BANDS / 4; ++j) dst[(int64_t)4 * j * T] = src[4 * j * MEL_OUT_LD];
+        }
+    }
+};
+typedef _Float16 mel_h8_t __attribute__((ext_vector_type(8)));
+constexpr int MEL_TRACK_FIELDS = 5;      // maest_logmel_rows_f16's track table: sample offset, S, first frame f0, frame count n, row offset
+struct MelEpiRowsF16 {
+    const int64_t* __restrict__ tracks;          // [n_tracks][5]
+    const int32_t* __restrict__ block_start;     // [n_tracks + 1]: first block of each track, ceil(n / 64) blocks per track
+    int n_tracks;
+    int64_t total_in, total_rows;                // the packed input's samples, the packed output's rows
+    _Float16* __restrict__ rows_out;             // [total_rows][96]
+    _Float16* rows = nullptr;                    // the row of the block's first frame
+    int n_rows = 0;                              // frames of the block that are stored (<= 64)
+    // grid (block_start[n_tracks]): the block's track by bisection; a table entry outside the buffers stores nothing (and reads inside them)
+    __device__ __forceinline__ const float* locate(const float* wave_in, int& S, int& T, int& t0) {
+        const int bid = blockIdx.x;
+        int lo = 0, hi = n_tracks - 1;          // the last track whose first block is <= bid
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (block_start[mid] <= bid) lo = mid;
+            else hi = mid - 1;
+        }
+        const int64_t* tr = tracks + MEL_TRACK_FIELDS * lo;
+        const int64_t off = tr[0], s = tr[1], f0 = tr[2], n = tr[3], r0 = tr[4];
+        const int64_t j = bid - block_start[lo];
+        const bool ok = s > MEL_NFFT / 2 && s <= INT32_MAX - 4 * MEL_NFFT && off >= 0 && off + s <= total_in && f0 >= 0 && n >= 1 &&
+                        f0 + n <= 1 + s / MEL_HOP && r0 >= 0 && r0 + n <= total_rows && j >= 0 && MEL_FRAMES_PER_BLOCK * j < n;
+        if (!ok) {
+            S = (int)(total_in < INT32_MAX - 4 * MEL_NFFT ? total_in : INT32_MAX - 4 * MEL_NFFT);
+            T = 1 + S / MEL_HOP;
+            t0 = 0;
+            return wave_in;
+        }
+        S = (int)s;
+        T = 1 + S / MEL_HOP;
+        t0 = (int)(f0 + MEL_FRAMES_PER_BLOCK * j);
+        const int64_t left = n - MEL_FRAMES_PER_BLOCK * j;
+        n_rows = left < MEL_FRAMES_PER_BLOCK ? (int)left : MEL_FRAMES_PER_BLOCK;
+        rows = rows_out + (r0 + MEL_FRAMES_PER_BLOCK * j) * MEL_BANDS;
+        return wave_in + off;
+    }
+    __device__ __forceinline__ void store(const float* otile, int, int) const {
+        // 12 chunks of 8 bands per frame: chunk c = frame c / 12, bands 8 (c % 12) .. + 7 -- consecutive threads, consecutive 16 bytes
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const int c = threadIdx.x + 256 * r;
+            const int f = c / 12, m0 = 8 * (c - 12 * f);
+            if (f < n_rows) {
+                mel_h8_t h;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) h[i] = (_Float16)otile[(m0 + i) * MEL_OUT_LD + f];      // round to nearest even
+                *reinterpret_cast<mel_h8_t*>(rows + 8 * c) = h;
+            }
+        }
+    }
+};
+
 // Round 3 form: a wave transforms FOUR frames at a time, 16 lanes per frame and 16 complex points per lane, as 256 = 16 x 16:
 // a 16-point DFT over n1 in registers (twiddles of the 16-point transform are literals), the W256^(n2 k1) factors (per-lane
 // registers), ONE exchange through LDS (lane n2 writes column n2, lane k1 reads row k1), a 16-point DFT over n2 in registers.
@@ -200,13 +276,15 @@ constexpr int MEL_PWBINS = 272;                   // 257 bins + 15 zero bins (a 
 // mel projection runs over the four frames at once (a band and a half band per lane, filter weights in registers).  Per frame and
 // wave ~165 instructions (counted in the code object: ~650 per four frames) against ~800 for four radix-4 stages through LDS with
 // one frame per wave.
+// EPI::locate finds the block's clip, its first frame t0 and (in a ragged batch) the clip's S and T; EPI::store writes the tile
+template <class EPI>
 __global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict__ wave_in, int S, int T,
                                                      const float* __restrict__ window,
                                                      const float* __restrict__ twiddle,   // [512][2] exp(-2 pi i k / 512)
                                                      const int32_t* __restrict__ fb_start,
                                                      const int32_t* __restrict__ fb_len,
                                                      const float* __restrict__ fb_w, int fb_stride, float log_scale,
-                                                     float norm_mean, float norm_2std, float* __restrict__ out) {
+                                                     float norm_mean, float norm_2std, EPI epi) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l = lane & 15, grp = lane >> 4;
@@ -216,9 +294,8 @@ __global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict_
     float* otile = tw512 + 512;                                       // [96][65]
     char* xch = reinterpret_cast<char*>(otile + MEL_BANDS * MEL_OUT_LD) + wv * 4 * MEL_XFRAME;          // per wave: 4 frames
     // the power spectra of the four frames reuse the exchange tiles (2304 >= 1040 bytes per frame; a wave-level sync apart)
-    const int b = blockIdx.y;
-    const int t0 = blockIdx.x * MEL_FRAMES_PER_BLOCK;
-    const float* wsrc = wave_in + (int64_t)b * S;
+    int t0;
+    const float* wsrc = epi.locate(wave_in, S, T, t0);
     const bool interior = t0 > 0 && (t0 + MEL_FRAMES_PER_BLOCK) * MEL_HOP + MEL_NFFT / 2 <= S && t0 + MEL_FRAMES_PER_BLOCK <= T &&
                           (reinterpret_cast<uintptr_t>(wsrc) & 7) == 0;      // block-uniform
     cplx xin[16];          // the lane's 16 packed points as loaded: (even, odd) sample = (re, im)
@@ -371,16 +448,7 @@ __global__ __launch_bounds__(256, 2) void logmel_kernel(const float* __restrict_
     if (interior) frames(std::true_type{});
     else frames(std::false_type{});
     __syncthreads();
-    // ---- coalesced store of the [96][64] tile: thread = frame tid & 63 of bands (tid >> 6) + 4 j (256-byte runs along T)
-    {
-        const int tl = threadIdx.x & 63, m0 = threadIdx.x >> 6;
-        if (t0 + tl < T) {
-            float* dst = out + ((int64_t)b * MEL_BANDS + m0) * T + t0 + tl;
-            const float* src = otile + m0 * MEL_OUT_LD + tl;
-#pragma unroll
-            for (int j = 0; j < MEL_BANDS / 4; ++j) dst[(int64_t)4 * j * T] = src[4 * j * MEL_OUT_LD];
-        }
-    }
+    epi.store(otile, t0, T);           // ---- coalesced store of the [96][64] tile
 }
 
 
@@ -641,6 +709,48 @@ __global__ __launch_bounds__(256) void logmel_bwd_gather_kernel(const float* __r
     dwave[(int64_t)b * S + j] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------
+// Polyphase resampler (the front of maest_amd/mel_extractor.py: audio at any rate -> 16 kHz), torchaudio.functional.resample's
+// sinc_interp_hann with the rates reduced by their gcd (orig -> new): output j = new q + p of a track is
+//   y[j] = sum_k taps[p][k] xpad[orig q + k],   xpad = `width` zeros, x, `width + orig` zeros,
+// and the host keeps only each phase's non-zero band (|t| < lowpass_filter_width): tap i of phase p multiplies x[orig q + first[p] + i - width]
+// (zero outside the track).  One thread per output sample, the taps tap-major ([i][p]: a wave's consecutive phases read one run); fp32
+// products summed by fma in tap order.
+constexpr int RS_TRACK_FIELDS = 4;       // maest_resample's track table: input offset, input length, output offset, output length
+constexpr int RS_BLOCK = 256;            // output samples per block
+__global__ __launch_bounds__(RS_BLOCK) void resample_kernel(const float* __restrict__ in, int64_t total_in,
+                                                           const int64_t* __restrict__ tracks, const int32_t* __restrict__ block_start,
+                                                           int n_tracks, int orig, int nw, int width,
+                                                           const float* __restrict__ taps, const int32_t* __restrict__ first, int n_taps,
+                                                           float* __restrict__ out, int64_t total_out) {
+    const int bid = blockIdx.x;
+    int lo = 0, hi = n_tracks - 1;               // the last track whose first block is <= bid
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (block_start[mid] <= bid) lo = mid;
+        else hi = mid - 1;
+    }
+    const int64_t* tr = tracks + RS_TRACK_FIELDS * lo;
+    const int64_t off = tr[0], S = tr[1], o0 = tr[2], n_out = tr[3];
+    const int64_t j = (int64_t)(bid - block_start[lo]) * RS_BLOCK + threadIdx.x;
+    if (!(off >= 0 && S >= 1 && off + S <= total_in && o0 >= 0 && o0 + n_out <= total_out) || j < 0 || j >= n_out) return;
+    const int64_t q = j / nw;
+    const int p = (int)(j - q * nw);
+    const float* x = in + off;
+    const int64_t i0 = q * orig + first[p] - width;          // the input index of tap 0
+    float acc = 0.0f;
+    if (i0 >= 0 && i0 + n_taps <= S) {
+        for (int i = 0; i < n_taps; ++i) acc = __builtin_fmaf(taps[(int64_t)i * nw + p], x[i0 + i], acc);
+    } else {
+        for (int i = 0; i < n_taps; ++i) {
+            const int64_t k = i0 + i;
+            const float v = k >= 0 && k < S ? x[k] : 0.0f;
+            acc = __builtin_fmaf(taps[(int64_t)i * nw + p], v, acc);
+        }
+    }
+    out[o0 + j] = acc;
+}
+
 }  // namespace maest
 
 using namespace maest;
@@ -655,9 +765,9 @@ extern "C" int maest_logmel(const float* wave, int B, int S, const float* window
     const int smem_bytes = (512 + 512 + 512 + MEL_BANDS * MEL_OUT_LD) * 4 + 4 * 4 * MEL_XFRAME;
     dim3 grid((T + MEL_FRAMES_PER_BLOCK - 1) / MEL_FRAMES_PER_BLOCK, B);
     static DeviceOnce once;                       // 70 KiB of dynamic LDS: above the 64 KiB a kernel gets without the attribute
-    ensure_dynamic_lds(once, &logmel_kernel, smem_bytes);
-    hipLaunchKernelGGL(logmel_kernel, grid, dim3(256), smem_bytes, (hipStream_t)stream, wave, S, T, window, twiddle,
-                       fb_start, fb_len, fb_w, fb_stride, log_scale, norm_mean, norm_2std, out);
+    ensure_dynamic_lds(once, &logmel_kernel<MelEpiBandMajor>, smem_bytes);
+    hipLaunchKernelGGL(logmel_kernel<MelEpiBandMajor>, grid, dim3(256), smem_bytes, (hipStream_t)stream, wave, S, T, window, twiddle,
+                       fb_start, fb_len, fb_w, fb_stride, log_scale, norm_mean, norm_2std, MelEpiBandMajor{out});
     return check_launch("maest_logmel");
 }
 
@@ -681,4 +791,39 @@ extern "C" int maest_logmel_bwd(const float* wave, const float* grad_out, int B,
     if (rc != 0) return rc;
     hipLaunchKernelGGL(logmel_bwd_gather_kernel, dim3((S + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, work, S, T, dwave);
     return check_launch("maest_logmel_bwd (gather)");
+}
+
+extern "C" int maest_logmel_rows_f16(const float* wave, int64_t total_in, const int64_t* tracks, const int32_t* block_start, int n_tracks,
+                                     int n_blocks, const float* window, const float* twiddle, const int32_t* fb_start, const int32_t* fb_len,
+                                     const float* fb_w, int fb_stride, float log_scale, void* rows, int64_t total_rows, void* stream) {
+    MAEST_REQUIRE(wave && tracks && block_start && window && twiddle && fb_start && fb_len && fb_w && rows,
+                  "maest_logmel_rows_f16: null pointer");
+    MAEST_REQUIRE(n_tracks > 0 && n_blocks > 0, "maest_logmel_rows_f16: bad shape n_tracks=%d n_blocks=%d", n_tracks, n_blocks);
+    MAEST_REQUIRE(total_in > MEL_NFFT / 2, "maest_logmel_rows_f16: bad shape total_in=%lld (reflect padding needs S > 256)",
+                  (long long)total_in);
+    MAEST_REQUIRE(total_rows > 0, "maest_logmel_rows_f16: bad shape total_rows=%lld", (long long)total_rows);
+    MAEST_REQUIRE(fb_stride > 0, "maest_logmel_rows_f16: bad fb_stride");
+    MAEST_REQUIRE((reinterpret_cast<uintptr_t>(rows) & 15) == 0, "maest_logmel_rows_f16: rows must be 16-byte aligned");
+    const int smem_bytes = (512 + 512 + 512 + MEL_BANDS * MEL_OUT_LD) * 4 + 4 * 4 * MEL_XFRAME;
+    static DeviceOnce once;
+    ensure_dynamic_lds(once, &logmel_kernel<MelEpiRowsF16>, smem_bytes);
+    MelEpiRowsF16 epi{tracks, block_start, n_tracks, total_in, total_rows, static_cast<_Float16*>(rows)};
+    // log10(1 + s mel): the forward's epilogue with mean 0 and 2 std 1
+    hipLaunchKernelGGL(logmel_kernel<MelEpiRowsF16>, dim3(n_blocks), dim3(256), smem_bytes, (hipStream_t)stream, wave, 0, 0, window,
+                       twiddle, fb_start, fb_len, fb_w, fb_stride, log_scale, 0.0f, 1.0f, epi);
+    return check_launch("maest_logmel_rows_f16");
+}
+
+extern "C" int maest_resample(const float* in, int64_t total_in, const int64_t* tracks, const int32_t* block_start, int n_tracks,
+                              int n_blocks, int orig, int new_rate, int width, const float* taps, const int32_t* first, int n_taps,
+                              float* out, int64_t total_out, void* stream) {
+    MAEST_REQUIRE(in && tracks && block_start && taps && first && out, "maest_resample: null pointer");
+    MAEST_REQUIRE(n_tracks > 0 && n_blocks > 0 && total_in > 0 && total_out > 0,
+                  "maest_resample: bad shape n_tracks=%d n_blocks=%d total_in=%lld total_out=%lld", n_tracks, n_blocks,
+                  (long long)total_in, (long long)total_out);
+    MAEST_REQUIRE(orig > 0 && new_rate > 0 && width >= 0 && n_taps > 0 && n_taps <= 2 * width + orig,
+                  "maest_resample: bad filter orig=%d new=%d width=%d n_taps=%d", orig, new_rate, width, n_taps);
+    hipLaunchKernelGGL(resample_kernel, dim3(n_blocks), dim3(RS_BLOCK), 0, (hipStream_t)stream, in, total_in, tracks, block_start,
+                       n_tracks, orig, new_rate, width, taps, first, n_taps, out, total_out);
+    return check_launch("maest_resample");
 }

@@ -551,6 +551,37 @@ def logmel_bwd(wave: torch.Tensor, grad: torch.Tensor, consts) -> torch.Tensor:
     return dwave
 
 
+def logmel_rows_f16(wave: torch.Tensor, tracks: torch.Tensor, block_start: torch.Tensor, n_blocks: int, total_rows: int,
+                    consts) -> torch.Tensor:
+    """Ragged log-mel into the on-disk mel file's rows: wave fp32 [total_in] (tracks packed), tracks int64 [n, 5] = (sample offset, S,
+    first frame, frame count, row offset), block_start int32 [n + 1] (ceil(count / 64) blocks per track) -> fp16 [total_rows, 96] =
+    log10(1 + 1e4 mel), no z-norm (csrc/mel.hip: logmel_kernel<MelEpiRowsF16>).  Rows no track covers are left unwritten."""
+    _chk(wave, tracks, block_start)
+    assert wave.dtype == torch.float32 and wave.dim() == 1
+    assert tracks.dtype == torch.int64 and tracks.dim() == 2 and tracks.shape[1] == 5 and block_start.dtype == torch.int32
+    n = int(tracks.shape[0])
+    assert block_start.numel() == n + 1
+    rows = torch.empty((total_rows, 96), dtype=torch.float16, device=wave.device)
+    _timed_call("maest_logmel_rows_f16", 0.0, _p(wave), wave.numel(), _p(tracks), _p(block_start), n, n_blocks, _p(consts.window),
+                _p(consts.twiddle), _p(consts.fb_start), _p(consts.fb_len), _p(consts.fb_w), consts.fb_stride, consts.log_scale, _p(rows),
+                total_rows, _s(wave))
+    return rows
+
+
+def resample(x: torch.Tensor, tracks: torch.Tensor, block_start: torch.Tensor, n_blocks: int, filt, out: torch.Tensor) -> torch.Tensor:
+    """Ragged polyphase resampling into `out` (fp32, written where the table points): x fp32 [total_in] (tracks packed), tracks int64
+    [n, 4] = (input offset, input length, output offset, output length), block_start int32 [n + 1] (256 outputs per block); `filt` =
+    mel_extractor.ResampleFilter on x.device (csrc/mel.hip: resample_kernel)."""
+    _chk(x, tracks, block_start, out)
+    assert x.dtype == torch.float32 and x.dim() == 1 and out.dtype == torch.float32 and out.dim() == 1
+    assert tracks.dtype == torch.int64 and tracks.dim() == 2 and tracks.shape[1] == 4 and block_start.dtype == torch.int32
+    n = int(tracks.shape[0])
+    assert block_start.numel() == n + 1
+    _timed_call("maest_resample", 0.0, _p(x), x.numel(), _p(tracks), _p(block_start), n, n_blocks, filt.orig, filt.new, filt.width,
+                _p(filt.taps), _p(filt.first), filt.n_taps, _p(out), out.numel(), _s(x))
+    return out
+
+
 def scale_(x: torch.Tensor, alpha: float):
     _chk(x)
     assert x.dtype == torch.float32
