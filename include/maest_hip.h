@@ -96,7 +96,9 @@ int maest_kernel_forms(int* mask);
 #define MAEST_OPT_GEMM_EPILOGUE 2
 #define MAEST_OPT_ATTN_BWD 3 /* env MAEST_ATTN_BWD, default 0: fused one-pass attention backward where it applies
                                 (bf16, N <= 320), query tiles fed by LDS-DMA; 1 = always the two-kernel dK/dV + dQ
-                                form; (2 selected the register-fed fused form, removed in round 6: now as 0;)
+                                form; (2 selected the register-fed fused form, removed in round 6: the library maps 2 to 0
+                                wherever a value enters -- environment, maest_set_option, maest_set_option_thread --, so
+                                maest_get_option reports 0;)
                                 3 = as 0 without the persistent form (one workgroup per (batch, head) at every shape).
                                 4 = as 1 with the register-staged padded tiles (the bf16 two-kernel form otherwise streams its
                                 tiles by LDS-DMA, bit-equal; A/B and tests).

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import threading
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -87,28 +88,37 @@ _host_emulation = False  # set only by tests/emu
 # for the calls it makes inside `with flavour("f16"):` (maest.py: precision="fp16" evaluation forwards); tensors keep the bf16 dtype TAG -- a
 # 16-bit container whose bits the kernels of the selected build interpret.
 LIB_PATH_F16 = os.environ.get("MAEST_HIP_LIB_F16") or os.path.join(_HERE, "libmaest_hip_f16.so")
-import threading as _threading
-_tls = _threading.local()
 
 
-class flavour:
-    """``with _lib.flavour("f16"): ...`` -- C-ABI calls of this thread go to libmaest_hip_f16.so inside the block."""
+class _Thread(threading.local):
+    def __init__(self):     # flavour(): the build this thread's C-ABI calls go to; thread_options(): its overrides, name -> value
+        self.flavour, self.options = "bf16", {}
 
-    def __init__(self, name):
-        assert name in ("bf16", "f16")
-        self.name = name
+
+_tls = _Thread()
+
+
+class _Block:
+    """A `with` block that sets values through `put(key, value)`; on exit each key gets back the value `get(key)` gave before it."""
+
+    def __init__(self, get, put, kw):
+        self.get, self.put, self.kw = get, put, kw
 
     def __enter__(self):
-        self.prev = getattr(_tls, "flavour", "bf16")
-        _tls.flavour = self.name
+        self.prev = {k: self.get(k) for k in self.kw}
+        for k, v in self.kw.items():
+            self.put(k, v)
         return self
 
     def __exit__(self, *a):
-        _tls.flavour = self.prev
+        for k, v in self.prev.items():
+            self.put(k, v)
 
 
-def current_flavour():
-    return getattr(_tls, "flavour", "bf16")
+def flavour(name):
+    """``with _lib.flavour("f16"): ...`` -- C-ABI calls of this thread go to libmaest_hip_f16.so inside the block."""
+    assert name in ("bf16", "f16")
+    return _Block(lambda k: getattr(_tls, k), lambda k, v: setattr(_tls, k, v), {"flavour": name})
 
 
 class MaestHipError(RuntimeError):
@@ -127,34 +137,40 @@ def _bind(lib):
     return lib
 
 
+def _open(path, missing):
+    """Bind the build at `path` and bring its switches to this process's state: the values of set_option, the overrides of the
+    binding thread's thread_options blocks."""
+    if not os.path.exists(path):
+        raise MaestHipError(missing)
+    lib = _bind(ctypes.CDLL(path))
+    if lib.maest_version() != ABI_VERSION:
+        raise MaestHipError(f"{os.path.basename(path)} ABI version mismatch")
+    for name, v in _set.items():
+        lib.maest_set_option(OPTIONS[name], v or 0, v is None)
+    for name, v in _tls.options.items():
+        lib.maest_set_option_thread(OPTIONS[name], v or 0, v is None)
+    return lib
+
+
 def load():
     """Load (once) and return the bound library -- the build the calling thread's flavour selects; raise loudly when it is absent."""
     global _lib, _lib_f16
-    if getattr(_tls, "flavour", "bf16") == "f16" and not _host_emulation:
+    if _tls.flavour == "f16" and not _host_emulation:
         if _lib_f16 is None:
-            if not os.path.exists(LIB_PATH_F16):
-                raise MaestHipError(f"{LIB_PATH_F16} not found: precision=\"fp16\" needs the half-precision build of the kernels "
-                                    "(`python -c 'import __graft_entry__ as g; g.build()'` builds both).")
-            _lib_f16 = _bind(ctypes.CDLL(LIB_PATH_F16))
-            if _lib_f16.maest_version() != ABI_VERSION:
-                raise MaestHipError("libmaest_hip_f16.so ABI version mismatch")
+            _lib_f16 = _open(LIB_PATH_F16, f"{LIB_PATH_F16} not found: precision=\"fp16\" needs the half-precision build of the kernels "
+                                           "(`python -c 'import __graft_entry__ as g; g.build()'` builds both).")
         return _lib_f16
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise MaestHipError(
-                f"{LIB_PATH} not found: the MI355X kernels are not built. Run "
-                "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
-                "maest_amd has no CPU fallback.")
-        _lib = _bind(ctypes.CDLL(LIB_PATH))
-        if _lib.maest_version() != ABI_VERSION:
-            raise MaestHipError("libmaest_hip.so ABI version mismatch")
+        _lib = _open(LIB_PATH, f"{LIB_PATH} not found: the MI355X kernels are not built. Run "
+                               "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc). "
+                               "maest_amd has no CPU fallback.")
     return _lib
 
 
 def _testing_override(path):
     """tests/emu only: bind a host-emulation build of the same sources."""
     global _lib, _host_emulation
-    _lib = _bind(ctypes.CDLL(path))
+    _lib = _open(path, path)
     _host_emulation = True
     return _lib
 
@@ -171,9 +187,14 @@ def host_emulation():
 
 def kernel_forms():
     """Bit mask of the owned-register kernels present in this build (include/maest_hip.h: MAEST_FORM_*)."""
-    m = c_int(0)
-    call("maest_kernel_forms", ctypes.byref(m))
-    return m.value
+    return _out_int("maest_kernel_forms")
+
+
+def _out_int(name, *args):
+    """The int that entry point `name` writes through its last argument."""
+    c = c_int(0)
+    call(name, *args, ctypes.byref(c))
+    return c.value
 
 
 def call(name, *args):
@@ -181,3 +202,47 @@ def call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         raise MaestHipError(f"{name} failed (status {rc}): {lib.maest_last_error().decode()}")
+
+
+# ------------------------------------------------------------------------------------ library switches (include/maest_hip.h)
+# Every write goes to every bound build, and _open brings a build bound later (the f16 one at the first fp16 forward) to the same state:
+# one value per name holds for both.  get_option, on the hot path (per wgrad GEMM, per backward block), does not cross the C ABI.
+_set = {}       # set_option: name -> value, None = the environment default
+_values = {}    # name -> process-wide value as the library reports it (maest_get_option), read once after each set_option
+
+
+def set_option(name: str, value: int | None):
+    """maest_set_option on every bound build; a build bound later starts from the values set here (_open replays them, so a missing f16
+    build still fails only when an fp16 forward asks for it).  `value` None restores the default (environment, read once at first use)."""
+    v = _set[name] = None if value is None else int(value)
+    for lib in filter(None, (_lib, _lib_f16)):
+        lib.maest_set_option(OPTIONS[name], v or 0, v is None)
+    _values.pop(name, None)
+
+
+def get_option(name: str) -> int:
+    """This thread's override of the switch (thread_options), else its process-wide value."""
+    v = _tls.options.get(name)
+    if v is None and (v := _values.get(name)) is None:      # (no override on this thread: the library reports the process-wide value)
+        v = _values[name] = _out_int("maest_get_option", OPTIONS[name])
+    return v
+
+
+def _set_thread(name, value):
+    """maest_set_option_thread on every build: `value` None clears this thread's override."""
+    _tls.options[name] = v = None if value is None else int(value)      # (first: a build that the read below binds replays it)
+    for lib in filter(None, (_lib, _lib_f16)):
+        lib.maest_set_option_thread(OPTIONS[name], v or 0, v is None)
+    _tls.options[name] = v if v is None else _out_int("maest_get_option", OPTIONS[name])    # the value as the library maps it
+
+
+def options(**kw):
+    """``with ops.options(gemm_min_m=512): ...`` -- set switches for a block, restore the previous values after."""
+    return _Block(_set.get, set_option, kw)
+
+
+def thread_options(**kw):
+    """``with ops.thread_options(gemm_wgs=256): ...`` -- override switches for launches made by THIS thread inside the block
+    (maest_set_option_thread); other threads see the process-wide values.  Blocks nest: on exit each switch gets back the override it
+    had before the block, or none."""
+    return _Block(lambda k: _tls.options.get(k), _set_thread, kw)

@@ -38,11 +38,14 @@ static std::atomic<int> g_option[kNumOptions];
 static int g_option_env[kNumOptions];
 static std::once_flag g_option_once;
 
+// where values enter the table: MAEST_OPT_ATTN_BWD = 2 (the register-fed fused backward, retired) is taken as 0
+static int option_value(int opt, int value) { return opt == MAEST_OPT_ATTN_BWD && value == 2 ? 0 : value; }
+
 static void options_init() {
     std::call_once(g_option_once, [] {
         for (int i = 0; i < kNumOptions; ++i) {
             const char* e = getenv(kOptionEnv[i]);
-            g_option_env[i] = e ? atoi(e) : kOptionDefault[i];
+            g_option_env[i] = option_value(i, e ? atoi(e) : kOptionDefault[i]);
             g_option[i].store(g_option_env[i], std::memory_order_relaxed);
         }
     });
@@ -64,14 +67,14 @@ int option(int opt) {
 extern "C" int maest_set_option(int opt, int value, int restore_default) {
     MAEST_REQUIRE(opt >= 0 && opt < maest::kNumOptions, "maest_set_option: unknown option %d", opt);
     maest::options_init();
-    maest::g_option[opt].store(restore_default ? maest::g_option_env[opt] : value, std::memory_order_relaxed);
+    maest::g_option[opt].store(restore_default ? maest::g_option_env[opt] : maest::option_value(opt, value), std::memory_order_relaxed);
     return MAEST_OK;
 }
 extern "C" int maest_set_option_thread(int opt, int value, int clear) {
     MAEST_REQUIRE(opt >= 0 && opt < maest::kNumOptions, "maest_set_option_thread: unknown option %d", opt);
     if (clear) maest::t_option_mask &= ~(1u << opt);
     else {
-        maest::t_option[opt] = value;
+        maest::t_option[opt] = maest::option_value(opt, value);
         maest::t_option_mask |= 1u << opt;
     }
     return MAEST_OK;

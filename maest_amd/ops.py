@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import BF16, BF16_QS, F32X3_A3, SPLIT3_A, SPLIT3_B, EPI_ATOMIC, EPI_MUL, EPI_GELU, EPI_NONE, EPI_RESIDUAL, F16, F32, F32X3, call
+from ._lib import get_option, options, set_option, thread_options  # noqa: F401  (the library switches: _lib.py)
 
 DT = {torch.float32: F32, torch.bfloat16: BF16}
 SPLIT3 = "split3"     # output "dtype" of the LayerNorm / attention-forward wrappers and of cast_weights_multi: the split-bf16 operand rows of
@@ -641,61 +642,3 @@ def swa_update_multi(avgs, curs, inv_count: float):
     a_n = (ctypes.c_int64 * n)(*[a.numel() for a in avgs])
     call("maest_swa_update_multi", n, ctypes.cast(a_avg, ctypes.c_void_p), ctypes.cast(a_cur, ctypes.c_void_p),
          ctypes.cast(a_n, ctypes.c_void_p), float(inv_count), _s(avgs[0]))
-
-
-# ------------------------------------------------------------------------------------ process-wide switches
-def set_option(name: str, value: Optional[int]):
-    """maest_set_option: `value` None restores the default (environment, read once at first use)."""
-    opt = _lib.OPTIONS[name]
-    call("maest_set_option", opt, 0 if value is None else int(value), 1 if value is None else 0)
-    _option_cache.pop((id(_lib.load()), name), None)
-
-
-# library switches change only through set_option (their environment defaults are read once by the library): the hot path
-# (one query per wgrad GEMM and per block of a backward pass) reads them from here instead of crossing the C ABI each time
-_option_cache = {}
-
-
-def get_option(name: str) -> int:
-    key = (id(_lib.load()), name)
-    v = _option_cache.get(key)
-    if v is None:
-        c = ctypes.c_int(0)
-        call("maest_get_option", _lib.OPTIONS[name], ctypes.byref(c))
-        v = _option_cache[key] = c.value
-    return v
-
-
-class thread_options:
-    """``with ops.thread_options(gemm_wgs=256): ...`` -- override switches for launches made by THIS thread inside the block
-    (maest_set_option_thread); other threads, and this thread afterwards, see the process-wide values.  Not re-entrant per switch."""
-
-    def __init__(self, **kw):
-        self.kw = kw
-
-    def __enter__(self):
-        for k, v in self.kw.items():
-            call("maest_set_option_thread", _lib.OPTIONS[k], int(v), 0)
-        return self
-
-    def __exit__(self, *a):
-        for k in self.kw:
-            call("maest_set_option_thread", _lib.OPTIONS[k], 0, 1)
-
-
-class options:
-    """``with ops.options(gemm_min_m=512): ...`` -- set switches for a block, restore the previous values after."""
-
-    def __init__(self, **kw):
-        self.kw = kw
-        self.prev = {}
-
-    def __enter__(self):
-        for k, v in self.kw.items():
-            self.prev[k] = get_option(k)
-            set_option(k, v)
-        return self
-
-    def __exit__(self, *a):
-        for k, v in self.prev.items():
-            set_option(k, v)
