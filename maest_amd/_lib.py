@@ -155,8 +155,11 @@ def _open(path, missing):
 def load():
     """Load (once) and return the bound library -- the build the calling thread's flavour selects; raise loudly when it is absent."""
     global _lib, _lib_f16
-    if _tls.flavour == "f16" and not _host_emulation:
+    if _tls.flavour == "f16":
         if _lib_f16 is None:
+            if _host_emulation:       # (never the bf16 emulator build in its place: its kernels would read the half bits as bfloat16)
+                raise MaestHipError("flavour(\"f16\") under host emulation, but no half-precision emulator build is bound "
+                                    "(_testing_override(path, path_f16))")
             _lib_f16 = _open(LIB_PATH_F16, f"{LIB_PATH_F16} not found: precision=\"fp16\" needs the half-precision build of the kernels "
                                            "(`python -c 'import __graft_entry__ as g; g.build()'` builds both).")
         return _lib_f16
@@ -167,17 +170,19 @@ def load():
     return _lib
 
 
-def _testing_override(path):
-    """tests/emu only: bind a host-emulation build of the same sources."""
-    global _lib, _host_emulation
+def _testing_override(path, path_f16=None):
+    """tests/emu only: bind a host-emulation build of the same sources -- and, with `path_f16`, its half-precision flavour, which
+    flavour("f16") calls then go to (without it they raise)."""
+    global _lib, _lib_f16, _host_emulation
     _lib = _open(path, path)
+    _lib_f16 = _open(path_f16, path_f16) if path_f16 else None
     _host_emulation = True
     return _lib
 
 
 def _testing_restore():
-    global _lib, _host_emulation
-    _lib = None
+    global _lib, _lib_f16, _host_emulation
+    _lib = _lib_f16 = None
     _host_emulation = False
 
 

@@ -155,10 +155,46 @@ static inline emu_f32x4 emu_mfma_f32_16x16x4f32(float a, float b, emu_f32x4 c, i
     emu::wave_sync();
     return c;
 }
+// the IEEE-half twins (the -DMAEST_16BIT_F16 build, common.h: MAEST_MFMA_*): the same lane layouts and summation order on _Float16 operands
+typedef __attribute__((ext_vector_type(8))) _Float16 emu_f16x8;
+static inline emu_f32x16 emu_mfma_f32_32x32x16_f16(emu_f16x8 a, emu_f16x8 b, emu_f32x16 c, int, int, int) {
+    emu::Wave& W = emu::wave();
+    const int l = emu::lane();
+    for (int j = 0; j < 8; ++j) { W.A[l][j] = (float)a[j]; W.B[l][j] = (float)b[j]; }
+    emu::wave_sync();
+    const int col = l & 31;
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5);
+        float s = c[r];
+        for (int k = 0; k < 16; ++k)
+            s += W.A[row + 32 * (k >> 3)][k & 7] * W.B[col + 32 * (k >> 3)][k & 7];
+        c[r] = s;
+    }
+    emu::wave_sync();
+    return c;
+}
+static inline emu_f32x4 emu_mfma_f32_16x16x32_f16(emu_f16x8 a, emu_f16x8 b, emu_f32x4 c, int, int, int) {
+    emu::Wave& W = emu::wave();
+    const int l = emu::lane();
+    for (int j = 0; j < 8; ++j) { W.A[l][j] = (float)a[j]; W.B[l][j] = (float)b[j]; }
+    emu::wave_sync();
+    const int col = l & 15;
+    for (int r = 0; r < 4; ++r) {
+        const int row = (l >> 4) * 4 + r;
+        float s = c[r];
+        for (int k = 0; k < 32; ++k)
+            s += W.A[row + 16 * (k >> 3)][k & 7] * W.B[col + 16 * (k >> 3)][k & 7];
+        c[r] = s;
+    }
+    emu::wave_sync();
+    return c;
+}
 #define __builtin_amdgcn_mfma_f32_32x32x16_bf16 emu_mfma_f32_32x32x16_bf16
 #define __builtin_amdgcn_mfma_f32_32x32x2f32 emu_mfma_f32_32x32x2f32
 #define __builtin_amdgcn_mfma_f32_16x16x32_bf16 emu_mfma_f32_16x16x32_bf16
 #define __builtin_amdgcn_mfma_f32_16x16x4f32 emu_mfma_f32_16x16x4f32
+#define __builtin_amdgcn_mfma_f32_32x32x16_f16 emu_mfma_f32_32x32x16_f16
+#define __builtin_amdgcn_mfma_f32_16x16x32_f16 emu_mfma_f32_16x16x32_f16
 
 // ds_read_b64_tr_b16 (gfx950), semantics probed on hardware (scratch/probe/tr_probe.hip): within each
 // 16-lane group, lane q supplies the address of 4 contiguous b16 of row q/4 (column chunk q%4) of a

@@ -4,6 +4,11 @@ Every case runs ONE C-ABI entry point through maest_amd.ops and compares it with
 (oracle/maest_oracle.py) or with the one-line torch definition of the op, in fp32 on the CPU.
 Tolerances: fp32 ("parity") mode 2e-5 relative unless stated; bf16 mode is checked against the
 same math evaluated on bf16-ROUNDED operands (so the only difference is accumulation order).
+
+The same cases run under the half-precision build (`with _lib.flavour("f16")`, libmaest_hip_f16.so): there a tensor tagged
+torch.bfloat16 is the 16-bit operand CONTAINER whose bits the kernels read as IEEE half.  Every 16-bit operand is made with lp()
+and read back with f32(), which follow the calling thread's build; 16-bit tolerances come from t16(bf16 value, f16 value).
+(A tensor tagged torch.float16 is something else: the loader's half mel input, MAEST_F16, in both builds.)
 """
 import math
 
@@ -21,11 +26,85 @@ def rnd(shape, seed, scale=1.0):
     return torch.from_numpy(rng.standard_normal(shape, dtype=np.float32) * np.float32(scale))
 
 
+def f16_build():
+    """Whether the calling thread's C-ABI calls go to the half-precision build (_lib.flavour("f16"))."""
+    return _lib._tls.flavour == "f16"
+
+
+def lp(t, dtype=torch.bfloat16):
+    """fp32 -> `dtype`; for the 16-bit operand type (torch.bfloat16) the container of the calling thread's build: bfloat16, or the
+    IEEE half bits (round to nearest even, +-inf past 65504, subnormals kept) tagged torch.bfloat16."""
+    if dtype != torch.bfloat16:
+        return t.to(dtype)
+    return t.half().view(torch.bfloat16) if f16_build() else t.bfloat16()
+
+
+def f32(t):
+    """The inverse of lp(): a tensor -> its fp32 values, a 16-bit container read as the calling thread's build reads it."""
+    if t.dtype == torch.bfloat16 and f16_build():
+        return t.view(torch.float16).float()
+    return t.float()
+
+
+def t16(bf, f16):
+    """A tolerance of a 16-bit result: `bf` in the bf16 build, `f16` (at most a quarter of it) in the half build."""
+    assert f16 * 4 <= bf, (bf, f16)
+    return f16 if f16_build() else bf
+
+
+_errs = None     # record(): what -> worst error / reference maximum of the close() / note() calls inside the block
+
+
+class record:
+    """``with record() as errs:`` -- collect, per `what`, the worst |got - ref| / max |ref| that close() and note() see."""
+
+    def __enter__(self):
+        global _errs
+        self.prev, _errs = _errs, {}
+        return _errs
+
+    def __exit__(self, *a):
+        global _errs
+        _errs = self.prev
+
+
+def note(what, got, ref):
+    """Record (no assertion) the error of `got` against ref(), a reference on UNROUNDED operands -- where the two builds differ by their
+    operand rounding although the case's own reference (on rounded operands) leaves them both at fp32 noise."""
+    if _errs is not None:
+        a, b = f32(got.detach()).cpu().double(), ref().detach().cpu().double()
+        e = float((a - b).abs().max()) / (float(b.abs().max()) + 1e-30)
+        _errs[what] = max(_errs.get(what, 0.0), e)
+
+
+CONTROL_FLOOR = 1e-4     # bf16-build errors below this (relative to the output's maximum) are fp32 accumulation noise: not compared
+
+
+def controlled(case, *args, **kw):
+    """Run `case` in the half build, then on the same inputs in the bf16 build, and require every error the bf16 build shows above
+    fp32 noise to be at least 4x smaller in the half build: a case cannot pass because the flavour switch was ignored, or because one
+    constant, conversion or mnemonic of the half build still works in bf16.  Returns {what: (err f16, err bf16)}."""
+    with record() as e16, _lib.flavour("f16"):
+        case(*args, **kw)
+    with record() as ebf:
+        case(*args, **kw)
+    both = {w: (e16[w], ebf[w]) for w in e16 if ebf.get(w, 0.0) > CONTROL_FLOOR}
+    assert both, f"{case.__name__}: no result above fp32 noise to compare the two builds on"
+    worst = max(both, key=lambda w: both[w][0] / both[w][1])
+    print(f"{case.__name__}: worst f16 error {max(e16.values()):.2e}; closest to the control: {worst!r} f16 {both[worst][0]:.2e} "
+          f"vs bf16 {both[worst][1]:.2e} (ratio {both[worst][1] / max(both[worst][0], 1e-30):.1f})")
+    bad = {w: v for w, v in both.items() if not v[0] * 4 < v[1]}
+    assert not bad, f"{case.__name__}: half build not 4x closer than bf16 (err f16, err bf16): {bad}"
+    return both
+
+
 def close(a, b, rtol, atol, what):
-    a = a.detach().float().cpu()
-    b = b.detach().float().cpu()
+    a = f32(a.detach()).cpu()
+    b = f32(b.detach()).cpu()
     assert a.shape == b.shape, (what, a.shape, b.shape)
     err = (a - b).abs()
+    if _errs is not None:
+        _errs[what] = max(_errs.get(what, 0.0), float(err.max()) / (float(b.abs().max()) + 1e-30))
     lim = atol + rtol * b.abs()
     bad = err > lim
     assert not bool(bad.any()), (
@@ -39,14 +118,15 @@ def tol(dtype):
 
 # ------------------------------------------------------------------------------------------ GEMM
 def case_gemm(dev, dtype, M, N, K, seed=0, identity=True):
-    a = rnd((M, K), seed).to(dtype)
-    b = rnd((N, K), seed + 1).to(dtype)
+    a = lp(rnd((M, K), seed), dtype)
+    b = lp(rnd((N, K), seed + 1), dtype)
     bias = rnd((N,), seed + 2)
-    ref = a.float() @ b.float().t() + bias
+    ref = f32(a) @ f32(b).t() + bias
     # fp32 accumulation-order noise of a K-term dot product of N(0,1) operands: ~ 4e-7 * K absolute
     rt, at = 1e-5, 4e-7 * K / math.sqrt(K / 64)
     c = ops.gemm_nt(a.to(dev), b.to(dev), bias.to(dev), out_dtype=torch.float32)
     close(c, ref, rt, at * math.sqrt(K / 64), "gemm none")
+    note("gemm none (unrounded operands)", c, lambda: rnd((M, K), seed).double() @ rnd((N, K), seed + 1).double().t() + bias.double())
     # asymmetric A = I check of the output orientation
     if identity and M >= K and dtype == torch.float32:
         eye = torch.zeros(M, K)
@@ -56,7 +136,7 @@ def case_gemm(dev, dtype, M, N, K, seed=0, identity=True):
     # GELU epilogue with aux_out
     aux = torch.empty((M, N), dtype=dtype, device=dev)
     g = ops.gemm_nt(a.to(dev), b.to(dev), bias.to(dev), out_dtype=dtype, epi=ops.EPI_GELU, aux_out=aux)
-    rt2, at2 = (1e-5, at) if dtype == torch.float32 else (1e-2, 1e-2)
+    rt2, at2 = (1e-5, at) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))
     xr = ref.clone().requires_grad_(True)
     F.gelu(xr).sum().backward()
     close(aux, xr.grad, rt2, max(at2 * math.sqrt(K / 64), 2e-6), "gemm gelu aux (= gelu' saved for backward)")
@@ -67,9 +147,9 @@ def case_gemm(dev, dtype, M, N, K, seed=0, identity=True):
                     aux_in=res.to(dev))
     close(c, ref + res, rt, at * math.sqrt(K / 64), "gemm residual")
     # mul epilogue (dgrad through GELU: acc * saved gelu')
-    pre = rnd((M, N), seed + 4).to(dtype)
+    pre = lp(rnd((M, N), seed + 4), dtype)
     c = ops.gemm_nt(a.to(dev), b.to(dev), None, out_dtype=dtype, epi=ops.EPI_MUL, aux_in=pre.to(dev))
-    close(c, (ref - bias) * pre.float(), rt2, at2 * math.sqrt(K / 64), "gemm mul")
+    close(c, (ref - bias) * f32(pre), rt2, at2 * math.sqrt(K / 64), "gemm mul")
     # split-K atomic accumulate
     acc = torch.zeros((M, N), dtype=torch.float32, device=dev)
     ops.gemm_nt(a.to(dev), b.to(dev), None, out=acc, epi=ops.EPI_ATOMIC, split_k=3)
@@ -84,14 +164,14 @@ def _same_products(new, old, exact, what, K=64):
     if exact:
         assert torch.equal(new, old), what
         return
-    a, b = new.float(), old.float()
+    a, b = f32(new), f32(old)
     scale = float(b.abs().max()) + 1e-30
     diff = (a - b).abs()
     if new.dtype == torch.float32:
         assert float(diff.max()) <= 4e-7 * math.sqrt(K) * scale + 1e-30, f"{what}: max |diff| {float(diff.max()):.3e} of scale {scale:.3e}"
     else:
-        ulp = 2.0 ** -7 * torch.maximum(a.abs(), b.abs()) + 1e-30          # one bf16 ulp is 2^-8 .. 2^-7 of the value
-        assert bool((diff <= ulp).all()), f"{what}: more than one bf16 ulp apart (max ratio {float((diff / ulp).max()):.2f})"
+        ulp = t16(2.0 ** -7, 2.0 ** -10) * torch.maximum(a.abs(), b.abs()) + 1e-30      # one 16-bit ulp is 2^-8 .. 2^-7 (half: 2^-11 .. 2^-10) of the value
+        assert bool((diff <= ulp).all()), f"{what}: more than one 16-bit ulp apart (max ratio {float((diff / ulp).max()):.2f})"
         assert float((diff > 0).float().mean()) <= 0.02, f"{what}: {100 * float((diff > 0).float().mean()):.2f} % of the elements differ"
 
 
@@ -100,12 +180,12 @@ def case_gemm_one_wave_per_simd(dev, M, N, K, seed=11, only=None, pair=True, bot
     (gemm_variant = 3): the same products summed in the same order and the same epilogue arithmetic -- bit for bit, in every
     epilogue form, ragged last tile row included -- and against the oracle's fp32 matmul."""
     dt = torch.bfloat16
-    a = rnd((M, K), seed).to(dt).to(dev)
-    w = (rnd((N, K), seed + 1) * 0.1).to(dt).to(dev)
+    a = lp(rnd((M, K), seed), dt).to(dev)
+    w = lp(rnd((N, K), seed + 1) * 0.1, dt).to(dev)
     bias = rnd((N,), seed + 2).to(dev)
     res = rnd((M, N), seed + 3).to(dev)
-    mul = rnd((M, N), seed + 4).to(dt).to(dev)
-    ref = a.float().cpu() @ w.float().cpu().t() + bias.cpu()
+    mul = lp(rnd((M, N), seed + 4), dt).to(dev)
+    ref = f32(a).cpu() @ f32(w).cpu().t() + bias.cpu()
     forms = [("none -> bf16", dict(out_dtype=dt)), ("none -> fp32", dict(out_dtype=torch.float32)),
              ("gelu -> bf16", dict(out_dtype=dt, epi=ops.EPI_GELU)), ("gelu -> fp32", dict(out_dtype=torch.float32, epi=ops.EPI_GELU)),
              ("residual -> fp32", dict(out_dtype=torch.float32, epi=ops.EPI_RESIDUAL, aux_in=res)),
@@ -130,41 +210,41 @@ def case_gemm_one_wave_per_simd(dev, M, N, K, seed=11, only=None, pair=True, bot
         g_o = ops.gemm_nt(a, w, bias, out_dtype=dt, epi=ops.EPI_GELU, aux_out=aux_o)
     _same_products(g_n, g_o, str(dev) == "cpu", "GELU of the pair form differs between the two 256 x 256 kernels", K)
     _same_products(aux_n, aux_o, str(dev) == "cpu", "GELU' of the pair form differs between the two 256 x 256 kernels", K)
-    close(g_n, F.gelu(ref), 1e-2, 1e-2 * math.sqrt(K / 64), "one-wave-per-SIMD GEMM: gelu")
+    close(g_n, F.gelu(ref), t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3) * math.sqrt(K / 64), "one-wave-per-SIMD GEMM: gelu")
 
 
 def case_gemm_rowdot(dev, dtype, M, N, K, ntok, seed=7):
     """maest_gemm_nt_rowdot: C = A B^T + bias in `dtype`, and rowdot[item, 64-column group, row in item] = the dot
     product of the STORED row segment of C with `other` -- the attention backward's delta out of the dgrad GEMM's
     epilogue.  Reference: the products of the returned C itself (exactly the values the kernel multiplied)."""
-    a = rnd((M, K), seed).to(dtype)
-    b = rnd((N, K), seed + 1).to(dtype)
+    a = lp(rnd((M, K), seed), dtype)
+    b = lp(rnd((N, K), seed + 1), dtype)
     bias = rnd((N,), seed + 2)
-    other = rnd((M, N), seed + 3).to(dtype)
+    other = lp(rnd((M, N), seed + 3), dtype)
     c, rd = ops.gemm_nt_rowdot(a.to(dev), b.to(dev), other.to(dev), ntok, out_dtype=dtype, bias=bias.to(dev))
-    ref = a.float() @ b.float().t() + bias
-    rt, at = (1e-5, 4e-7 * K) if dtype == torch.float32 else (1e-2, 1e-2 * math.sqrt(K / 64))
+    ref = f32(a) @ f32(b).t() + bias
+    rt, at = (1e-5, 4e-7 * K) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3) * math.sqrt(K / 64))
     close(c, ref, rt, at, "gemm rowdot: C")
     assert rd.shape == (M // ntok, N // 64, ntok)
-    want = (c.float().cpu() * other.float()).reshape(M // ntok, ntok, N // 64, 64).sum(-1).permute(0, 2, 1)
-    close(rd, want, 1e-5, 1e-5 * math.sqrt(64) * float(c.float().abs().max()), "gemm rowdot: per-(row, group) dot products")
+    want = (f32(c).cpu() * f32(other)).reshape(M // ntok, ntok, N // 64, 64).sum(-1).permute(0, 2, 1)
+    close(rd, want, 1e-5, 1e-5 * math.sqrt(64) * float(f32(c).abs().max()), "gemm rowdot: per-(row, group) dot products")
     if dtype == torch.bfloat16:
         # bf16: the call above took gemm_nt256o_kernel where the shape has 256-row tiles; the 8-wave kernel's row-dot epilogue does the
         # same arithmetic in the same order
         with ops.options(gemm_variant=3):
             c3, rd3 = ops.gemm_nt_rowdot(a.to(dev), b.to(dev), other.to(dev), ntok, out_dtype=dtype, bias=bias.to(dev))
         _same_products(c, c3, str(dev) == "cpu", "row-dot epilogue: C differs between the one-wave-per-SIMD and 8-wave kernels", K)
-        close(rd, rd3, 1e-2, 1e-2 * math.sqrt(64) * float(c.float().abs().max()) * 2.0 ** -7, "row-dot epilogue: dot products of the two kernels")
+        close(rd, rd3, t16(1e-2, 2.5e-3), 1e-2 * math.sqrt(64) * float(f32(c).abs().max()) * t16(2.0 ** -7, 2.0 ** -10), "row-dot epilogue: dot products of the two kernels")
 
 
 def case_gemm_tn(dev, dtype, K, M, N, seed=3, lda_pad=0, splits=(1, 3, 0)):
     """wgrad form: out[M,N] += a[K,M]^T b[K,N], colsum[M] += a.sum(0); ragged K (token tail)."""
-    a_full = rnd((K, M + lda_pad), seed).to(dtype)
+    a_full = lp(rnd((K, M + lda_pad), seed), dtype)
     a = a_full[:, :M]
-    b = rnd((K, N), seed + 1).to(dtype)
-    ref = a.float().t() @ b.float()
-    ref_cs = a.float().sum(0)
-    at = 4e-7 * K + (0 if dtype == torch.float32 else 1e-3)
+    b = lp(rnd((K, N), seed + 1), dtype)
+    ref = f32(a).t() @ f32(b)
+    ref_cs = f32(a).sum(0)
+    at = 4e-7 * K + (0 if dtype == torch.float32 else t16(1e-3, 2.5e-4))
     for sk in splits:
         out = torch.zeros((M, N), dtype=torch.float32, device=dev)
         cs = torch.zeros(M, dtype=torch.float32, device=dev)
@@ -172,6 +252,8 @@ def case_gemm_tn(dev, dtype, K, M, N, seed=3, lda_pad=0, splits=(1, 3, 0)):
         ops.gemm_tn(a_dev, b.to(dev), out, colsum=cs, split_k=sk, M=M, N=N)
         close(out, ref, 1e-5, at, f"gemm_tn split_k={sk}")
         close(cs, ref_cs, 1e-5, at, f"gemm_tn colsum split_k={sk}")
+        note("gemm_tn (unrounded operands)", out, lambda: rnd((K, M + lda_pad), seed)[:, :M].double().t() @ rnd((K, N), seed + 1).double())
+        note("gemm_tn colsum (unrounded operands)", cs, lambda: rnd((K, M + lda_pad), seed)[:, :M].double().sum(0))
     # the deterministic split-K combine of the 256-tile kernel (tn_reduce=1; where the shape takes it): partial tiles through a
     # workspace, summed in split order by a second kernel -- bit-reproducible, and ACCUMULATING into `out` like the atomics
     a_dev, b_dev = a_full.to(dev)[:, :M], b.to(dev)
@@ -197,16 +279,16 @@ def case_gemm_tn(dev, dtype, K, M, N, seed=3, lda_pad=0, splits=(1, 3, 0)):
 
 # ------------------------------------------------------------------------------------- transposes
 def case_transpose(dev, dtype, rows, cols):
-    src = rnd((rows, cols), 5).to(dtype)
+    src = lp(rnd((rows, cols), 5), dtype)
     ld = ops.round_up(rows, 64)
     out = ops.transpose(src.to(dev), ld)
     assert out.shape == (cols, ld)
     close(out[:, :rows], src.t(), 0, 0, "transpose")
-    assert float(out[:, rows:].float().abs().sum()) == 0.0, "transpose pad must be zero"
+    assert float(f32(out[:, rows:]).abs().sum()) == 0.0, "transpose pad must be zero"
     w = rnd((rows, cols), 6)
     d, dt_ = ops.cast_weights(w.to(dev), dtype, want=True, want_t=True)
-    close(d, w.to(dtype), 0, 0, "cast")
-    close(dt_, w.to(dtype).t(), 0, 0, "cast transposed")
+    close(d, lp(w, dtype), 0, 0, "cast")
+    close(dt_, lp(w, dtype).t(), 0, 0, "cast transposed")
     # many parameters, one launch (ragged shapes, NULL outputs)
     # (sides that are multiples of 4 take the kernel's quad path -- 16-byte loads, 8-byte stores --, the others the element-wise one)
     ws = [rnd((rows, cols), 60), rnd((cols, 33), 61), rnd((65, 64), 62), rnd((132, 72), 63), rnd((64, 256), 64)]
@@ -215,9 +297,9 @@ def case_transpose(dev, dtype, rows, cols):
         for t, (o, ot) in zip(ws, outs):
             assert (o is None) == (not want) and (ot is None) == (not want_t)
             if o is not None:
-                close(o, t.to(dtype), 0, 0, "cast multi")
+                close(o, lp(t, dtype), 0, 0, "cast multi")
             if ot is not None:
-                close(ot, t.to(dtype).t(), 0, 0, "cast multi transposed")
+                close(ot, lp(t, dtype).t(), 0, 0, "cast multi transposed")
 
 
     # leading rows of the PLAIN copy scaled before the rounding (the q rows of a qkv projection, MAEST_BF16_QS); the transposed copy is not
@@ -225,8 +307,8 @@ def case_transpose(dev, dtype, rows, cols):
         (o, ot), = ops.cast_weights_multi([t.to(dev)], dtype, want=True, want_t=True, scaled_rows=[40], row_scale=0.1803)
         want_o = t.clone()
         want_o[:40] *= 0.1803
-        close(o, want_o.to(dtype), 0, 0, "cast multi, scaled leading rows")
-        close(ot, t.to(dtype).t(), 0, 0, "cast multi, transposed copy unscaled")
+        close(o, lp(want_o, dtype), 0, 0, "cast multi, scaled leading rows")
+        close(ot, lp(t, dtype).t(), 0, 0, "cast multi, transposed copy unscaled")
 
 
 # --------------------------------------------------------------------------------------- LayerNorm
@@ -236,15 +318,15 @@ def case_layernorm(dev, dtype, rows):
     b = rnd((768,), 9, 0.1)
     y, mean, rstd = ops.layernorm_fwd(x.to(dev), g.to(dev), b.to(dev), 1e-6, dtype, save_stats=True)
     ref = F.layer_norm(x, (768,), g, b, 1e-6)
-    rt, at = (1e-5, 1e-5) if dtype == torch.float32 else (1e-2, 1e-2)
+    rt, at = (1e-5, 1e-5) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))
     close(y, ref, rt, at, "layernorm fwd")
     close(mean, x.mean(1), 1e-5, 1e-6, "layernorm mean")
     close(rstd, 1.0 / torch.sqrt(x.var(1, unbiased=False) + 1e-6), 1e-5, 1e-6, "layernorm rstd")
     # residual add fused into the LayerNorm that follows it: x_new = x + delta exactly (one fp32 add per element),
     # y / statistics = those of the plain kernel on x_new, bit for bit
-    delta = rnd((rows, 768), 12, 0.5).to(dtype)
+    delta = lp(rnd((rows, 768), 12, 0.5), dtype)
     xn, y2, mean2, rstd2 = ops.add_layernorm_fwd(x.to(dev), delta.to(dev), g.to(dev), b.to(dev), 1e-6, dtype, save_stats=True)
-    assert torch.equal(xn.cpu(), x + delta.float()), "fused residual add must be the exact fp32 sum"
+    assert torch.equal(xn.cpu(), x + f32(delta)), "fused residual add must be the exact fp32 sum"
     y3, mean3, rstd3 = ops.layernorm_fwd(xn, g.to(dev), b.to(dev), 1e-6, dtype, save_stats=True)
     assert torch.equal(y2, y3) and torch.equal(mean2, mean3) and torch.equal(rstd2, rstd3)
     if dtype == torch.float32:
@@ -252,26 +334,26 @@ def case_layernorm(dev, dtype, rows):
         # hi = bf16(y), lo = bf16(y - hi) of the fp32 result, from both kernels
         s3 = ops.layernorm_fwd(x.to(dev), g.to(dev), b.to(dev), 1e-6, ops.SPLIT3).cpu()
         yf = y.cpu()
-        hi = yf.bfloat16()
-        lo = (yf - hi.float()).bfloat16()
+        hi = lp(yf)
+        lo = lp(yf - f32(hi))
         assert s3.shape == (rows, 2304) and s3.dtype == torch.bfloat16
         assert torch.equal(s3[:, :768], hi) and torch.equal(s3[:, 768:1536], hi) and torch.equal(s3[:, 1536:], lo), "layernorm split3 rows"
         xn3, s3b = ops.add_layernorm_fwd(x.to(dev), delta.to(dev), g.to(dev), b.to(dev), 1e-6, ops.SPLIT3)
         y2f = y2.cpu()
-        hi2 = y2f.bfloat16()
-        assert torch.equal(xn3, xn) and torch.equal(s3b.cpu(), torch.cat([hi2, hi2, (y2f - hi2.float()).bfloat16()], 1)), "add + layernorm split3 rows"
+        hi2 = lp(y2f)
+        assert torch.equal(xn3, xn) and torch.equal(s3b.cpu(), torch.cat([hi2, hi2, lp(y2f - f32(hi2))], 1)), "add + layernorm split3 rows"
     # backward
-    dy = rnd((rows, 768), 10).to(dtype)
+    dy = lp(rnd((rows, 768), 10), dtype)
     dres = rnd((rows, 768), 11)
     xr = x.clone().requires_grad_(True)
     gr = g.clone().requires_grad_(True)
     br = b.clone().requires_grad_(True)
-    F.layer_norm(xr, (768,), gr, br, 1e-6).backward(dy.float())
+    F.layer_norm(xr, (768,), gr, br, 1e-6).backward(f32(dy))
     dg = torch.zeros(768, device=dev)
     db = torch.zeros(768, device=dev)
     dx, dx_lp = ops.layernorm_bwd(dy.to(dev), x.to(dev), g.to(dev), mean, rstd, dres.to(dev), dg, db, lp_dtype=dtype)
     close(dx, xr.grad + dres, 1e-4, 1e-5, "layernorm dx")
-    close(dx_lp, xr.grad + dres, *( (1e-4, 1e-5) if dtype == torch.float32 else (1e-2, 1e-2)), "layernorm dx_lp")
+    close(dx_lp, xr.grad + dres, *((1e-4, 1e-5) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))), "layernorm dx_lp")
     close(dg, gr.grad, 1e-4, 1e-4 * math.sqrt(rows), "layernorm dgamma")
     close(db, br.grad, 1e-4, 1e-4 * math.sqrt(rows), "layernorm dbeta")
     # compact residual gradient (the first 2 tokens of every clip of n_tok tokens; zero for the others): bit for bit
@@ -301,23 +383,26 @@ def _attn_ref(qkv, B, N, scale):
 
 
 def case_attention(dev, dtype, B, N, seed=20, spike=False, bf16_tol=3e-2, fwd_tol=2e-2, qs=False):
-    """qs (bf16 only): the MAEST_BF16_QS contract -- the q columns of the tensor handed to the kernels hold q' = scale * log2(e) * q
+    """16-bit tolerances: bf16_tol / fwd_tol in the bf16 build, an eighth of them in the half build.
+    qs (bf16 only): the MAEST_BF16_QS contract -- the q columns of the tensor handed to the kernels hold q' = scale * log2(e) * q
     (rounded once); the oracle runs on q = q' / (scale * log2(e)) and dQ is compared as the gradient with respect to that q."""
     assert not qs or dtype == torch.bfloat16
     attn_fwd, attn_bwd = partial(ops.attn_fwd, q_prescaled=qs), partial(ops.attn_bwd, q_prescaled=qs)
-    qkv = rnd((B * N, 2304), seed, 1.0).to(dtype)
+    if dtype != torch.float32:
+        bf16_tol, fwd_tol = t16(bf16_tol, bf16_tol / 8), t16(fwd_tol, fwd_tol / 8)
+    qkv = lp(rnd((B * N, 2304), seed, 1.0), dtype)
     if spike:  # force a large running-max jump at a late key tile (online-softmax rescale branch)
-        qf = qkv.float().clone()
+        qf = f32(qkv).clone()
         key = min(N - 1, 70)
         qf[key, 768:768 + 64] = qf[3, 0:64] * 6.0
-        qkv = qf.to(dtype)
+        qkv = lp(qf, dtype)
     scale = 0.125
-    x = qkv.float()
+    x = f32(qkv)
     if qs:
         c = scale * 1.4426950408889634
-        qp = (qkv[:, :768].float() * c).to(dtype)          # what the row-scaled projection writes
+        qp = lp(f32(qkv[:, :768]) * c, dtype)          # what the row-scaled projection writes
         qkv = torch.cat([qp, qkv[:, 768:]], dim=1).contiguous()
-        x = torch.cat([qp.float() / c, x[:, 768:]], dim=1)
+        x = torch.cat([f32(qp) / c, x[:, 768:]], dim=1)
     out, lse = attn_fwd(qkv.to(dev), B, N, scale, save_lse=True)
     x = x.requires_grad_(True)
     ref, ref_lse = _attn_ref(x, B, N, scale)
@@ -350,9 +435,9 @@ def case_attention(dev, dtype, B, N, seed=20, spike=False, bf16_tol=3e-2, fwd_to
                 outw, lsew = attn_fwd(qkv.to(dev), B, N, scale, save_lse=True)
             assert torch.equal(outw, out2) and torch.equal(lsew, lse2), f"attention forward with {nw} waves per workgroup differs"
     # backward (the oracle's autograd on the same rounded operands)
-    dout = rnd((B * N, 768), seed + 1).to(dtype)
-    ref.backward(dout.float())
-    out_ref_lp = ref.detach().to(dtype)
+    dout = lp(rnd((B * N, 768), seed + 1), dtype)
+    ref.backward(f32(dout))
+    out_ref_lp = lp(ref.detach(), dtype)
     dqkv = attn_bwd(qkv.to(dev), out_ref_lp.to(dev), dout.to(dev), ref_lse.detach().contiguous().to(dev), B, N, scale)
     rt, at = (1e-4, 1e-4) if dtype == torch.float32 else (bf16_tol, bf16_tol)
     g = x.grad
@@ -389,7 +474,7 @@ def case_attention(dev, dtype, B, N, seed=20, spike=False, bf16_tol=3e-2, fwd_to
         close(dq2[:, 1536:], g[:, 1536:], rt, at, "attention dV (two-kernel)")
         close(dq2[:, 768:1536], g[:, 768:1536], rt, at, "attention dK (two-kernel)")
         close(dq2[:, :768], g[:, :768], rt, at, "attention dQ (two-kernel)")
-        close(dqkv, dq2.float(), 2e-2, 2e-2, "fused vs two-kernel attention backward")
+        close(dqkv, f32(dq2), t16(2e-2, 2.5e-3), t16(2e-2, 2.5e-3), "fused vs two-kernel attention backward")
         if N > 256:
             # the default call above took the PERSISTENT form (one workgroup per CU walking its (batch, head) items); the
             # one-workgroup-per-item form against the oracle as well, and the two bit for bit (same sums in the same order)
@@ -405,8 +490,9 @@ def case_attention_head_rows(dev, dtype, B, N, seed=25):
     kernel): equal -- to bf16 rounding of the same sums -- to the complete backward fed a dO that is zero beyond row 2, with
     dQ = 0 for every other query; shapes the fused kernel does not serve are refused loudly."""
     from maest_amd._lib import MaestHipError
-    qkv = rnd((B * N, 2304), seed, 1.0).to(dtype).to(dev)
+    qkv = lp(rnd((B * N, 2304), seed, 1.0), dtype).to(dev)
     scale = 0.125
+    tl = 2e-2 if dtype == torch.float32 else t16(2e-2, 2.5e-3)      # (two kernels' roundings of the same sums)
     # (the complete pass in the four-wave form the restricted pass is a subset of: above 320 tokens the default complete pass
     # is the persistent kernel, equal to rounding only -- checked next)
     with ops.options(attn_fwd=2 if dtype == torch.bfloat16 else 0):
@@ -415,10 +501,11 @@ def case_attention_head_rows(dev, dtype, B, N, seed=25):
     nv = min(32, N)
     f3, p3 = full.reshape(B, N, 768), part.reshape(B, N, 768)
     assert torch.equal(p3[:, :nv], f3[:, :nv]), "restricted forward differs on the rows it computes"
+    note("restricted forward (unrounded operands)", p3[:, :nv], lambda: _attn_ref(rnd((B * N, 2304), seed, 1.0), B, N, scale)[0].reshape(B, N, 768)[:, :nv])
     assert torch.equal(lse_part[:, :, :nv], lse_full[:, :, :nv])
     dflt, lse_dflt = ops.attn_fwd(qkv, B, N, scale, save_lse=True)
-    close(dflt.float().cpu(), full.float().cpu(), 2e-2, 2e-2, "default complete forward vs four-wave form")
-    close(lse_dflt.cpu(), lse_full.cpu(), 1e-4, 2e-2, "default complete forward vs four-wave form (lse)")
+    close(dflt, full, tl, tl, "default complete forward vs four-wave form")
+    close(lse_dflt.cpu(), lse_full.cpu(), 1e-4, tl, "default complete forward vs four-wave form (lse)")
     # gather / scatter of the head tokens' rows
     comp = ops.gather_head_rows(full, B, N, 2)
     assert torch.equal(comp.reshape(B, 2, 768), f3[:, :2])
@@ -426,18 +513,18 @@ def case_attention_head_rows(dev, dtype, B, N, seed=25):
     assert torch.equal(back[:, :2], f3[:, :2]) and not back[:, 2:nv].any()
     xf = rnd((B * N, 768), seed + 3).to(dev)
     assert torch.equal(ops.gather_head_rows(xf, B, N, 2).reshape(B, 2, 768), xf.reshape(B, N, 768)[:, :2])
-    dout_c = rnd((B * 2, 768), seed + 1).to(dtype).to(dev)
+    dout_c = lp(rnd((B * 2, 768), seed + 1), dtype).to(dev)
     dense = ops.scatter_head_rows(dout_c, B, N, 2, N)          # zero everywhere else
     if ops.attn_bwd_rows_supported(dtype, N):
         want = ops.attn_bwd(qkv, full, dense, lse_full, B, N, scale)
         got = ops.attn_bwd(qkv, part, ops.scatter_head_rows(dout_c, B, N, 2, nv), lse_part, B, N, scale, q_rows=2)
-        close(got[:, 768:], want[:, 768:].float().cpu(), 2e-2, 2e-2, "restricted attention backward dK, dV")
+        close(got[:, 768:], want[:, 768:], tl, tl, "restricted attention backward dK, dV")
         g3, w3 = got.reshape(B, N, 2304), want.reshape(B, N, 2304)
-        close(g3[:, :2, :768], w3[:, :2, :768].float().cpu(), 2e-2, 2e-2, "restricted attention backward dQ")
+        close(g3[:, :2, :768], w3[:, :2, :768], tl, tl, "restricted attention backward dQ")
         assert not g3[:, 2:, :768].any(), "queries without gradient must get dQ = 0"
         with ops.options(attn_bwd=1):
             two = ops.attn_bwd(qkv, full, dense, lse_full, B, N, scale)
-        close(got[:, 768:], two[:, 768:].float().cpu(), 2e-2, 2e-2, "restricted fused vs complete two-kernel backward")
+        close(got[:, 768:], two[:, 768:], tl, tl, "restricted fused vs complete two-kernel backward")
     else:
         try:
             ops.attn_bwd(qkv, full, dense, lse_full, B, N, scale, q_rows=2)
@@ -496,7 +583,7 @@ def case_patch_embed(dev, dtype, B, T, patchout=0, mix=False, seed=30, masked=Fa
     if keep is not None:
         ref = ref[:, :, :, torch.from_numpy(keep).long()]
     ref = ref.permute(0, 2, 3, 1).reshape(B * Fp * Tk, 256)
-    close(cols, ref.to(dtype), 0, 1e-6 if dtype == torch.float32 else 0, "im2col")
+    close(cols, lp(ref, dtype), 0, 1e-6 if dtype == torch.float32 else 0, "im2col")
     # token assembly vs oracle.tokens_from_patches
     Tt = (62 if T <= 640 else T // 10) if stride[1] == 10 else Tp + 1
     sd = {"cls_token": rnd((1, 1, 768), 40, .02), "dist_token": rnd((1, 1, 768), 41, .02),
@@ -521,7 +608,7 @@ def case_patch_embed(dev, dtype, B, T, patchout=0, mix=False, seed=30, masked=Fa
     d_cls, d_dist, d_np, d_fp, d_tp = z(768), z(768), z(2, 768), z(768, Fp), z(768, Tt)
     dp = ops.token_assemble_bwd(dx0.to(dev), B, Fp, Tt, toff, tok_dev, dtype, d_cls, d_dist, d_np, d_fp, d_tp)
     gk = convg.grad if keep is None else convg.grad[:, :, :, torch.from_numpy(keep).long()]
-    close(dp, gk.permute(0, 2, 3, 1).reshape(B * Fp * Tk, 768), *((0, 1e-6) if dtype == torch.float32 else (1e-2, 1e-2)), "dpatches")
+    close(dp, gk.permute(0, 2, 3, 1).reshape(B * Fp * Tk, 768), *((0, 1e-6) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))), "dpatches")
     close(d_cls, sdg["cls_token"].grad.reshape(768), 1e-5, 1e-5, "d cls")
     close(d_dist, sdg["dist_token"].grad.reshape(768), 1e-5, 1e-5, "d dist")
     close(d_np, sdg["new_pos_embed"].grad.reshape(2, 768), 1e-5, 1e-5, "d new_pos")
@@ -575,10 +662,11 @@ def case_loss(dev, rows, cols):
     out = torch.zeros(cols, device=dev)
     ops.colsum(src.to(dev), out)
     close(out, src.sum(0), 1e-4, 1e-4, "colsum")
-    srcb = src.to(torch.bfloat16)
+    srcb = lp(src)
     out = torch.zeros(cols, device=dev)
     ops.colsum(srcb.to(dev), out)
-    close(out, srcb.float().sum(0), 1e-4, 1e-4, "colsum bf16")
+    close(out, f32(srcb).sum(0), 1e-4, 1e-4, "colsum bf16")
+    note("colsum 16-bit (unrounded operands)", out, lambda: src.double().sum(0))
     v = rnd((1000,), 63)
     w = ops.scale_(v.clone().to(dev), 0.25)
     close(w, v * 0.25, 0, 0, "scale")
@@ -714,17 +802,17 @@ def case_split_precision(dev, M=512, N=256, K=192, B=1, Ntok=75):
     e = (c.double().cpu() - ref).abs().max().item() / scale
     assert e < 1e-4, f"split-bf16 GEMM: {e:.2e} of the output scale"
     with ops.options(gemm_min_m=512):
-        c16 = ops.gemm_nt(a.bfloat16().to(dev), b.bfloat16().to(dev), bias.to(dev), out_dtype=torch.float32,
+        c16 = ops.gemm_nt(lp(a).to(dev), lp(b).to(dev), bias.to(dev), out_dtype=torch.float32,
                           epi=ops.EPI_RESIDUAL, aux_in=res.to(dev))
     e16 = (c16.double().cpu() - ref).abs().max().item() / scale
     assert e16 > 10 * e, f"plain bf16 operands ({e16:.2e}) should be far coarser than the split ({e:.2e})"
     # the same three-term product as ONE bf16 GEMM over 3 K (MAEST_SPLIT3_A x MAEST_SPLIT3_B rows; the bf16 kernels, fp32 output): the weight
     # rows come from maest_cast_weights_multi, the activation rows are built here as the LayerNorm / attention kernels write them
     b3 = ops.cast_weights_multi([b.to(dev)], ops.SPLIT3)[0][0]
-    bh = b.bfloat16()
-    assert torch.equal(b3.cpu(), torch.cat([bh, (b - bh.float()).bfloat16(), bh], 1)), "split3 weight rows"
-    ah = a.bfloat16()
-    a3 = torch.cat([ah, ah, (a - ah.float()).bfloat16()], 1).contiguous()
+    bh = lp(b)
+    assert torch.equal(b3.cpu(), torch.cat([bh, lp(b - f32(bh)), bh], 1)), "split3 weight rows"
+    ah = lp(a)
+    a3 = torch.cat([ah, ah, lp(a - f32(ah))], 1).contiguous()
     with ops.options(gemm_min_m=512):
         c3 = ops.gemm_nt(a3.to(dev), b3, bias.to(dev), out_dtype=torch.float32, epi=ops.EPI_RESIDUAL, aux_in=res.to(dev))
     e3 = (c3.double().cpu() - ref).abs().max().item() / scale
@@ -735,19 +823,19 @@ def case_split_precision(dev, M=512, N=256, K=192, B=1, Ntok=75):
         with ops.options(gemm_min_m=512 if big else 1 << 30):
             gf = ops.gemm_nt(a3.to(dev), b3, bias.to(dev), out_dtype=torch.float32, epi=ops.EPI_GELU).cpu()
             g3 = ops.gemm_nt(a3.to(dev), b3, bias.to(dev), out_dtype=ops.SPLIT3, epi=ops.EPI_GELU).cpu()
-        gh = gf.bfloat16()
+        gh = lp(gf)
         assert g3.shape == (M, 3 * N) and torch.equal(g3[:, :N], g3[:, N:2 * N]), "split3 rows: the two hi thirds"
         same_kernel = (not big) or ops.gemm_split3_out_fast(M, N, 3 * K)
         if same_kernel:      # both outputs left the same main loop: the split of the very fp32 values
-            assert torch.equal(g3, torch.cat([gh, gh, (gf - gh.float()).bfloat16()], 1)), f"GELU epilogue split3 rows (big = {big})"
+            assert torch.equal(g3, torch.cat([gh, gh, lp(gf - f32(gh))], 1)), f"GELU epilogue split3 rows (big = {big})"
         # (a build without the one-wave-per-SIMD kernel writes the fp32 form from the eight-wave kernel and the split form from the 128 x 128 one)
-        rec = g3[:, :N].double() + g3[:, 2 * N:].double()
+        rec = f32(g3[:, :N]).double() + f32(g3[:, 2 * N:]).double()
         assert (rec - gref).abs().max().item() / gref.abs().max().item() < 1e-4, "hi + lo of the split rows"
         assert (gf.double() - gref).abs().max().item() / gref.abs().max().item() < 1e-4
     o3 = ops.attn_fwd(qkv.to(dev), B, Ntok, 0.125, x3=True, out_split3=True).cpu()
     of = out.cpu()
-    oh = of.bfloat16()
-    assert torch.equal(o3, torch.cat([oh, oh, (of - oh.float()).bfloat16()], 1)), "attention forward split3 rows"
+    oh = lp(of)
+    assert torch.equal(o3, torch.cat([oh, oh, lp(of - f32(oh))], 1)), "attention forward split3 rows"
     oref, lref = oref.detach(), lref.detach()
     eo = (out.double().cpu() - oref).abs().max().item() / oref.abs().max().item()
     el = (lse.double().cpu() - lref).abs().max().item()
@@ -758,3 +846,135 @@ def case_split_precision(dev, M=512, N=256, K=192, B=1, Ntok=75):
     eo1 = (out1.double().cpu() - oref).abs().max().item() / oref.abs().max().item()
     assert eo1 < 1e-4 and (lse1.double().cpu() - lref).abs().max().item() < 1e-4, f"split-bf16 attention forward (per-use split): {eo1:.2e}"
     return e, eo
+
+
+# ------------------------------------------------------------------------------------- the half format's edges
+def _half_bits_equal(got, want_f32, what):
+    """`got` (a 16-bit container of the half build) holds exactly torch's .half() of `want_f32`: round to nearest even, +-inf past 65504,
+    subnormals kept (not flushed).  NaN compared as NaN."""
+    g = got.detach().cpu().view(torch.int16)
+    w = want_f32.detach().cpu().half().view(torch.int16)
+    nan = torch.isnan(want_f32.cpu())
+    same = (g == w) | (nan & torch.isnan(got.detach().cpu().view(torch.float16)))
+    if not bool(same.all()):
+        i = tuple(int(v) for v in (~same).nonzero()[0])
+        raise AssertionError(f"{what}: {int((~same).sum())} values differ from torch's .half(); first at {i}: fp32 {float(want_f32.cpu()[i])!r} -> "
+                             f"{float(got.detach().cpu().view(torch.float16)[i])!r}, want {float(want_f32.cpu()[i].half())!r}")
+
+
+# fp32 values at the half format's edges: around 65504 (the largest finite half; 65520 is the tie that rounds to inf), past it, the
+# smallest normal (6.1035e-5), the subnormal range down to its smallest step (5.96e-8) and the ties below it, and round-to-even ties
+EDGE_VALUES = [0.0, -0.0, 1.0, -1.0, 65504.0, -65504.0, 65519.99, -65519.99, 65520.0, -65520.0, 65535.0, 1.0e5, -3.0e38, 6.1035156e-5,
+               6.0e-5, -3.0e-5, 1.0e-5, 1.0e-6, -1.0e-7, 5.96e-8, 2.9802322e-8, 2.99e-8, 1.0e-8, 2049.0, 2051.0, 1.0009765625, 0.33333334]
+
+
+def edge_values(shape, seed):
+    """[shape] fp32: EDGE_VALUES first, then magnitudes log-uniform over 1e-9 .. 1e6 with random signs."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    n = int(np.prod(shape))
+    v = np.exp(rng.uniform(np.log(1e-9), np.log(1e6), n)) * rng.choice([-1.0, 1.0], n)
+    v[: len(EDGE_VALUES)] = EDGE_VALUES
+    return torch.from_numpy(v.astype(np.float32)).reshape(shape)
+
+
+def case_half_conversions(dev, M=512, N=256, K=64, forms=({},)):
+    """Half build: every fp32 -> 16-bit conversion of cast_weights(_multi), cast_rows and a GEMM's 16-bit output equals torch's .half()
+    bit for bit.  The GEMM's fp32 results are chosen: out[m, n] = x[m] * 1 + bias[n] with x half values (0, +-65504, 65472, the smallest
+    normal, ...) and fp32 biases, so that the sums straddle 65504 and fill the subnormal range; `forms`: ops.options of the kernels to
+    take (each its own epilogue conversion)."""
+    assert f16_build()
+    w = edge_values((70, 130), 300)
+    d, dt_ = ops.cast_weights(w.to(dev), torch.bfloat16, want=True, want_t=True)
+    _half_bits_equal(d, w, "cast_weights")
+    _half_bits_equal(dt_, w.t(), "cast_weights transposed")
+    ws = [edge_values((64, 256), 301), edge_values((33, 70), 302)]      # the quad path and the element-wise one
+    for t, (o, ot) in zip(ws, ops.cast_weights_multi([t.to(dev) for t in ws], torch.bfloat16, want=True, want_t=True)):
+        _half_bits_equal(o, t, "cast_weights_multi")
+        _half_bits_equal(ot, t.t(), "cast_weights_multi transposed")
+    r = ops.cast_rows(w.to(dev), torch.bfloat16, ld_dst=192)
+    _half_bits_equal(r[:, :130], w, "cast_rows")
+    assert not r[:, 130:].view(torch.int16).any(), "cast_rows pad must be zero"
+    xs = torch.tensor([0.0, 65504.0, -65504.0, 65472.0, 1.0, -1.0, 6.1035156e-5, -3.0517578e-5, 0.5, 1024.0, 65440.0, -65472.0])
+    x = torch.where(torch.arange(M) < 2 * len(xs), xs[torch.arange(M) % len(xs)], 0.0)     # (the rest: +0 + bias)
+    bs = torch.tensor([0.0, 16.0, 15.99, 31.99, 32.0, 47.99, 48.0, -16.0, -15.99, 1.0e-7, -1.0e-7, 5.0e-8, 3.0e-8, 6.0e-5, 1.0e-5, 7.0e4])
+    bias = torch.cat([bs, edge_values((N - len(bs),), 303) * 1e-3])
+    a = torch.zeros(M, K)
+    a[:, 0] = x
+    b = torch.zeros(N, K)
+    b[:, 0] = 1.0
+    want = x[:, None] + bias[None, :]          # the fp32 sums (one rounding, as the epilogue's acc + bias)
+    for kw in forms:
+        with ops.options(**kw):
+            c = ops.gemm_nt(lp(a).to(dev), lp(b).to(dev), bias.to(dev), out_dtype=torch.bfloat16)
+        _half_bits_equal(c, want, f"gemm 16-bit output {kw}")
+
+
+def _finite_except(t, bad, what):
+    """Every element of `t` (a container or fp32) where `bad` is True is inf or NaN, every other one finite."""
+    v = f32(t.detach()).cpu()
+    fin = torch.isfinite(v)
+    assert not bool(fin[bad].any()), f"{what}: {int(fin[bad].sum())} of {int(bad.sum())} outputs fed by an inf / NaN are finite"
+    assert bool(fin[~bad].all()), f"{what}: {int((~fin[~bad]).sum())} outputs no inf / NaN reaches are not finite"
+
+
+def case_nonfinite(dev, M=144, N=200, K=128, B=2, Ntok=40, rows=11, gemm_forms=({},), tn_forms=({},), attn_forms=({},)):
+    """An inf or NaN in one 16-bit operand row reaches every output it feeds as inf / NaN -- never a finite value, never 0 -- and no other:
+    the NT dgrad GEMM (fp32 and 16-bit output), the TN wgrad GEMM and its column sums (split-K, the workspace combine), the attention
+    backward with one inf in dO (delta = rowsum(dO * O), dS = P * (dP - delta)) and layernorm_bwd.  GradScaler finds an overflowed step
+    only through this.  *_forms: ops.options of the kernel forms to take."""
+    inf, nan = float("inf"), float("nan")
+    a = rnd((M, K), 400)
+    a[3, 5], a[7, 9] = inf, nan
+    b = rnd((N, K), 401)
+    bad = torch.zeros(M, N, dtype=torch.bool)
+    bad[3], bad[7] = True, True
+    for kw in gemm_forms:
+        with ops.options(**kw):
+            for od in (torch.float32, torch.bfloat16):
+                _finite_except(ops.gemm_nt(lp(a).to(dev), lp(b).to(dev), None, out_dtype=od), bad, f"gemm_nt -> {od} {kw}")
+    # wgrad: out[m, n] = sum_k a[k, m] b[k, n], colsum[m] = sum_k a[k, m]
+    ta, tb = rnd((K, M), 402), rnd((K, N), 403)
+    ta[4, 10] = inf
+    tb[6, 20] = nan
+    bad = torch.zeros(M, N, dtype=torch.bool)
+    bad[10], bad[:, 20] = True, True
+    bad_cs = torch.zeros(M, dtype=torch.bool)
+    bad_cs[10] = True
+    for kw in tn_forms:
+        for sk in (1, 0):
+            with ops.options(**kw):
+                out = torch.zeros((M, N), dtype=torch.float32, device=dev)
+                cs = torch.zeros(M, dtype=torch.float32, device=dev)
+                ops.gemm_tn(lp(ta).to(dev), lp(tb).to(dev), out, colsum=cs, split_k=sk)
+            _finite_except(out, bad, f"gemm_tn split_k={sk} {kw}")
+            _finite_except(cs, bad_cs, f"gemm_tn colsum split_k={sk} {kw}")
+    # attention backward: dO[clip 0, query 5, head 2, d 7] = inf
+    qkv = lp(rnd((B * Ntok, 2304), 404))
+    dout = rnd((B * Ntok, 768), 405)
+    dout[5, 2 * 64 + 7] = inf
+    bad = torch.zeros(B, Ntok, 3, 12, 64, dtype=torch.bool)
+    bad[0, 5, 0, 2] = True          # dQ of that query, head 2
+    bad[0, :, 1, 2] = True          # dK of every key of clip 0, head 2
+    bad[0, :, 2, 2, 7] = True       # dV[:, d = 7] of every key of clip 0, head 2
+    bad = bad.reshape(B * Ntok, 2304)
+    for kw in attn_forms:
+        with ops.options(**kw):
+            o, lse = ops.attn_fwd(qkv.to(dev), B, Ntok, 0.125, save_lse=True)
+            d = ops.attn_bwd(qkv.to(dev), o, lp(dout).to(dev), lse, B, Ntok, 0.125)
+        _finite_except(d, bad, f"attention backward {kw}")
+    # layernorm backward: dy[3, 11] = inf
+    x = rnd((rows, 768), 406, 2.0) + 0.3
+    g, bb = 1.0 + rnd((768,), 407, 0.1), rnd((768,), 408, 0.1)
+    _, mean, rstd = ops.layernorm_fwd(x.to(dev), g.to(dev), bb.to(dev), 1e-6, torch.bfloat16, save_stats=True)
+    dy = rnd((rows, 768), 409)
+    dy[3, 11] = inf
+    dg, db = torch.zeros(768, device=dev), torch.zeros(768, device=dev)
+    dx, dx_lp = ops.layernorm_bwd(lp(dy).to(dev), x.to(dev), g.to(dev), mean, rstd, None, dg, db, lp_dtype=torch.bfloat16)
+    bad = torch.zeros(rows, 768, dtype=torch.bool)
+    bad[3] = True
+    _finite_except(dx, bad, "layernorm_bwd dx")
+    _finite_except(dx_lp, bad, "layernorm_bwd dx (16-bit)")
+    bad_c = torch.zeros(768, dtype=torch.bool)
+    bad_c[11] = True
+    _finite_except(dg, bad_c, "layernorm_bwd dgamma")
+    _finite_except(db, bad_c, "layernorm_bwd dbeta")

@@ -327,6 +327,41 @@ def test_g5_training_step_in_fp16_with_a_scaled_loss():
     assert not torch.equal(net.blocks[3].mlp.fc1.weight, before) and l.item() < l0
 
 
+def test_g5_fp16_grad_scaler_skips_a_step_whose_half_gradients_overflow():
+    """GradScaler's contract with the half build: at a loss scale where the half gradients overflow (2^40) they must become inf / NaN and
+    reach the fp32 parameter gradients -- conversions that round to +-inf, never saturate at 65504, and no kernel that loses an inf or a
+    NaN -- so that scaler.step skips the step (parameters bit for bit unchanged) and update() lowers the scale; once the scale fits, a step
+    goes through with finite gradients."""
+    g = np.load(os.path.join(GOLD, "g5_train_step.npz"))
+    net = build("passt_s_swa_p16_128_ap476", 625, input_t=625, s_patchout_t=30, precision="fp16").train()
+    mod = Module(net=net, mixup_alpha=0.3)
+    x, y, mix, po = _g5_batch(g)
+    opt = mod.get_optimizer(net.parameters())
+    scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 40, backoff_factor=2.0 ** -6, growth_interval=1000)
+    before = {n: p.detach().clone() for n, p in net.named_parameters()}
+    scales = []
+    for i in range(8):
+        scale = scaler.get_scale()
+        l = mod.training_step((x, None, y), 0, _mixup=mix, _patchout=po)
+        scaler.scale(l).backward()
+        finite = all(bool(torch.isfinite(p.grad).all()) for p in net.parameters() if p.grad is not None)
+        scaler.step(opt)
+        scaler.update()
+        opt.zero_grad(set_to_none=True)
+        scales.append((scale, finite))
+        if scaler.get_scale() < scale:          # skipped
+            assert not finite, f"step {i}: scale lowered with finite gradients"
+            for n, p in net.named_parameters():
+                assert torch.equal(p, before[n]), f"step {i} was skipped but changed {n}"
+        else:
+            assert finite
+            break
+    print(f"GradScaler (scale, finite gradients) per step: {scales}")
+    assert not scales[0][1], "the half gradients at loss scale 2^40 stayed finite: an overflow was saturated or lost"
+    assert scales[-1][1], f"no step went through: {scales}"
+    assert any(not torch.equal(p, before[n]) for n, p in net.named_parameters()), "the step that went through changed nothing"
+
+
 def test_g5_teacher_student_step_fp32():
     g = np.load(os.path.join(GOLD, "g5_train_step_ts.npz"))
     net = build("discogs-maest-30s-pw-73e-ts", 625, n_classes=519, input_t=625, s_patchout_t=30,

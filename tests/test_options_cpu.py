@@ -140,7 +140,7 @@ sys.path.insert(0, {repo!r})
 from maest_amd import _lib, ops
 ops.set_option("gemm_min_m", 768)
 if {emu!r}:
-    _lib._testing_override({emu!r})
+    _lib._testing_override({emu!r}, {emu16!r})
 with ops.thread_options(gemm_wgs=6):          # (binds the bf16 build here, the f16 one below)
     for f in ["bf16"] + (["f16"] if {f16!r} else []):
         with _lib.flavour(f):
@@ -150,12 +150,14 @@ with ops.thread_options(gemm_wgs=6):          # (binds the bf16 build here, the 
 
 def test_a_build_bound_later_starts_from_the_values_set(lib):
     """Each build is bound once per process, so this runs in a fresh interpreter: set_option (and a thread override) before the build is
-    bound, then what the build itself reports; MAEST_ATTN_BWD=2 from the environment reads back as 0."""
+    bound, then what the build itself reports; MAEST_ATTN_BWD=2 from the environment reads back as 0.  Under emulation the child binds
+    both emulator builds, the half one for flavour("f16")."""
     from tests.emu import build_emu
     emu = build_emu.LIB if _lib.host_emulation() else ""
-    f16 = not emu and os.path.exists(_lib.LIB_PATH_F16)
+    emu16 = build_emu.build(f16=True) if emu else ""
+    f16 = bool(emu) or os.path.exists(_lib.LIB_PATH_F16)
     env = dict(os.environ, MAEST_ATTN_BWD="2")
-    r = subprocess.run([sys.executable, "-c", _CHILD.format(repo=REPO, emu=emu, f16=f16)], env=env, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, "-c", _CHILD.format(repo=REPO, emu=emu, emu16=emu16, f16=f16)], env=env, capture_output=True, text=True,
                        timeout=300)
     assert r.returncode == 0, r.stderr
     want = ["bf16 768 6 0"] + (["f16 768 6 0"] if f16 else [])
