@@ -394,6 +394,18 @@ int maest_augment_mel(const float* wave, int B, int S, const float* window, cons
                       const int32_t* fb_start, const int32_t* fb_len, const float* fb_w, int fb_stride,
                       int n_mels, float pre0, float pre1, float log_eps, float norm_add, float norm_div,
                       float* out, void* stream);
+/* Backward of maest_augment_mel (added within ABI version 9: a new entry, no existing one changes).
+ * grad_out: fp32 [B, n_mels, T] = dL/dout; dwave: fp32 [B, S] = dL/dwave (written, not accumulated).  The forward's arguments as there
+ * (norm_add does not enter the gradient and is not passed); bin_band: int32 [513, 2] and bin_w: fp32 [513, 2] = the transpose of the
+ * filterbank: the (at most two) bands of each FFT bin and their weights (an unused slot: band 0, weight 0).  work: fp32 scratch of
+ * work_elems >= B * T * 1024 floats (the windowed gradient of every frame before overlap-add).  Requires S > 513, 1 <= n_mels <= 128,
+ * fb_stride > 0.  Deterministic: every dwave sample is summed by one thread in a fixed order, both reflect folds and the pre-emphasis
+ * adjoint included; the spectrum is recomputed from wave, nothing is saved by the forward.  Masked stripes (training mode): zero them
+ * in a copy of grad_out first (maest_spec_mask); grad_out is only read. */
+int maest_augment_mel_bwd(const float* wave, const float* grad_out, int B, int S, const float* window, const float* twiddle,
+                          const int32_t* fb_start, const int32_t* fb_len, const float* fb_w, int fb_stride, int n_mels,
+                          const int32_t* bin_band, const float* bin_w, float pre0, float pre1, float log_eps, float norm_div,
+                          float* work, int64_t work_elems, float* dwave, void* stream);
 
 /* ---- optimizer-side helper: scale a flat fp32 gradient bucket (after the RCCL all-reduce) */
 int maest_scale_f32(float* x, int64_t n, float alpha, void* stream);

@@ -629,6 +629,25 @@ def augment_mel(wave, window, twiddle, fb_start, fb_len, fb_w, fb_stride, n_mels
     return out
 
 
+def augment_mel_bwd(wave, grad, window, twiddle, fb_start, fb_len, fb_w, fb_stride, n_mels, bin_band, bin_w, pre0, pre1, log_eps,
+                    norm_div) -> torch.Tensor:
+    """Backward of augment_mel: wave fp32 [B, S] (the forward's input), grad fp32 [B, n_mels, 1 + (S - 1) // 320] -> dwave fp32 [B, S].
+    bin_band int32 / bin_w fp32 [513, 2]: the transpose of the bank (preprocess.bin_bands).  Deterministic (one thread sums each sample; no
+    atomics).  Scratch: the windowed gradient of every frame, B * T * 4 KB."""
+    _chk(wave, grad, window, twiddle, fb_start, fb_len, fb_w, bin_band, bin_w)
+    assert wave.dtype == torch.float32 and wave.dim() == 2 and wave.is_contiguous()
+    assert grad.dtype == torch.float32 and grad.is_contiguous()
+    B, S = wave.shape
+    T = 1 + (S - 1) // 320
+    assert grad.shape == (B, n_mels, T), (tuple(grad.shape), (B, n_mels, T))
+    assert bin_band.dtype == torch.int32 and tuple(bin_band.shape) == (513, 2) and tuple(bin_w.shape) == (513, 2)
+    work = torch.empty(B * T * 1024, dtype=torch.float32, device=wave.device)
+    dwave = torch.empty((B, S), dtype=torch.float32, device=wave.device)
+    call("maest_augment_mel_bwd", _p(wave), _p(grad), B, S, _p(window), _p(twiddle), _p(fb_start), _p(fb_len), _p(fb_w), fb_stride,
+         n_mels, _p(bin_band), _p(bin_w), pre0, pre1, log_eps, norm_div, _p(work), work.numel(), _p(dwave), _s(wave))
+    return dwave
+
+
 def swa_update_multi(avgs, curs, inv_count: float):
     """avg += (cur - avg) * inv_count for every (avg, cur) pair of fp32 tensors, one launch."""
     _chk(*avgs, *curs)

@@ -14,6 +14,7 @@ import math
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -54,6 +55,54 @@ def sparse_bands(fb: np.ndarray):
     return np.asarray(starts, np.int32), np.asarray(lens, np.int32), w, stride
 
 
+def bin_bands(fb: np.ndarray, n_bins: int):
+    """The transpose of the bank for the backward (maest_augment_mel_bwd): [bands, bins] -> each bin's (at most two) bands int32
+    [n_bins, 2] and their weights fp32 [n_bins, 2]; bins beyond the bank's columns weigh 0."""
+    band = np.zeros((n_bins, 2), np.int32)
+    w = np.zeros((n_bins, 2), np.float32)
+    for k in range(fb.shape[1]):
+        nz = np.nonzero(fb[:, k])[0]
+        if len(nz) > 2:
+            raise NotImplementedError(f"bin {k} lies in {len(nz)} mel bands; the backward's per-bin table holds two")
+        band[k, : len(nz)] = nz
+        w[k, : len(nz)] = fb[nz, k]
+    return band, w
+
+
+class _AugmentMelFn(torch.autograd.Function):
+    """fp32 [B, S] -> [B, n_mels, T] with a backward (maest_augment_mel_bwd).  Only the waveform and the call's constants are saved: the
+    backward recomputes the spectrum.  ``stripes`` None: eval mode, log and (x + 4.5) / 5 inside the kernel; else (time, frequency)
+    stripes of training mode -- the forward is augment_mel(norm 0, 1) -> spec_mask_ -> affine_ (both in place, on a tensor autograd has
+    not seen yet), the backward zeroes the stripes in a copy of the upstream gradient; 1 / 5 rides in the kernel's norm_div."""
+
+    @staticmethod
+    def forward(ctx, w, consts, bands, stripes):
+        ctx.consts, ctx.bands, ctx.stripes = consts, bands, stripes
+        ctx.save_for_backward(w)
+        return _augment_mel(w, consts, bands, stripes)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (w,) = ctx.saved_tensors
+        win, tw, n_mels, pre0, pre1 = ctx.consts
+        st, ln, fw, stride, bband, bw = ctx.bands
+        g = g.float().contiguous()
+        if ctx.stripes is not None:
+            g = ops.spec_mask_(g.clone(), *ctx.stripes)
+        return ops.augment_mel_bwd(w, g, win, tw, st, ln, fw, stride, n_mels, bband, bw, pre0, pre1, 0.00001, 5.0), None, None, None
+
+
+def _augment_mel(w, consts, bands, stripes):
+    win, tw, n_mels, pre0, pre1 = consts
+    st, ln, fw, stride = bands[:4]
+    if stripes is None:                            # log, then (melspec + 4.5) / 5 inside the kernel
+        return ops.augment_mel(w, win, tw, st, ln, fw, stride, n_mels, pre0, pre1, 0.00001, 4.5, 5.0)
+    mel = ops.augment_mel(w, win, tw, st, ln, fw, stride, n_mels, pre0, pre1, 0.00001, 0.0, 1.0)
+    ops.spec_mask_(mel, *stripes)
+    return ops.affine_(mel, 4.5, 5.0)              # (melspec + 4.5) / 5
+
+
 class AugmentMelSTFT(nn.Module):
     def __init__(self, n_mels=128, sr=32000, win_length=800, hopsize=320, n_fft=1024, freqm=48, timem=192, htk=False,
                  fmin=0.0, fmax=None, norm=1, fmin_aug_range=1, fmax_aug_range=1000):
@@ -86,8 +135,10 @@ class AugmentMelSTFT(nn.Module):
                 self._fb_cache.clear()
             fb = kaldi_mel_banks(self.n_mels, self.n_fft, self.sr, fmin, fmax)     # [n_mels, 512]; bin 512 weighs 0
             st, ln, w, stride = sparse_bands(fb)
+            bband, bw = bin_bands(fb, self.n_fft // 2 + 1)
             self._fb_cache[key] = (torch.from_numpy(st).to(device), torch.from_numpy(ln).to(device),
-                                   torch.from_numpy(w).to(device), stride)
+                                   torch.from_numpy(w).to(device), stride,
+                                   torch.from_numpy(bband).to(device), torch.from_numpy(bw).to(device))
         return self._fb_cache[key]
 
     def _stripes(self, B, size, param, n=1):
@@ -103,18 +154,19 @@ class AugmentMelSTFT(nn.Module):
         fmax = self.fmax + self.fmax_aug_range // 2 - torch.randint(self.fmax_aug_range, (1,)).item()
         if not self.training:                          # don't augment eval data
             fmin, fmax = self.fmin, self.fmax
-        st, ln, w, stride = self._bands(fmin, fmax, x.device)
+        bands = self._bands(fmin, fmax, x.device)
         c = self.preemphasis_coefficient.reshape(-1).tolist()
         xw = x.float().contiguous()
-        win, tw = self.window.to(x.device), self.twiddle.to(x.device)
-        if not self.training:                          # log, then (melspec + 4.5) / 5 inside the kernel
-            return ops.augment_mel(xw, win, tw, st, ln, w, stride, self.n_mels, c[0], c[1], 0.00001, 4.5, 5.0)
-        mel = ops.augment_mel(xw, win, tw, st, ln, w, stride, self.n_mels, c[0], c[1], 0.00001, 0.0, 1.0)
-        B, F, T = mel.shape
-        fs = self._stripes(B, F, self.freqm) if self.freqm else None      # freqm first, then timem (:126-127)
-        ts = self._stripes(B, T, self.timem) if self.timem else None
-        ops.spec_mask_(mel, None if ts is None else ts.to(mel.device), None if fs is None else fs.to(mel.device))
-        return ops.affine_(mel, 4.5, 5.0)              # (melspec + 4.5) / 5
+        consts = (self.window.to(x.device), self.twiddle.to(x.device), self.n_mels, c[0], c[1])
+        stripes = None
+        if self.training:
+            B, F, T = xw.shape[0], self.n_mels, 1 + (xw.shape[1] - 1) // self.hopsize
+            fs = self._stripes(B, F, self.freqm) if self.freqm else None      # freqm first, then timem (:126-127)
+            ts = self._stripes(B, T, self.timem) if self.timem else None
+            stripes = (None if ts is None else ts.to(x.device), None if fs is None else fs.to(x.device))
+        if torch.is_grad_enabled() and xw.requires_grad:   # a waveform that wants a gradient (saliency, a loss behind a generator)
+            return _AugmentMelFn.apply(xw, consts, bands, stripes)
+        return _augment_mel(xw, consts, bands, stripes)
 
     def extra_repr(self):
         return "winsize={}, hopsize={}".format(self.win_length, self.hopsize)
