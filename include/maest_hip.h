@@ -436,6 +436,51 @@ int maest_melfile_assemble(const uint16_t* frames, const int64_t* row_start, con
                            int B, int n_bands, int T, int normalize, float norm_mean, float norm_div,
                            float* out, void* stream);
 
+/* ---- training-time regularisers: element dropout and stochastic depth (added within ABI version 9: new entries only) -----------
+ * Reference: MAEST(drop_rate=, drop_path_rate=), models/maest.py:452-454; pos_drop :800, Attention.proj_drop :354-377, Mlp.drop
+ * :200-207, DropPath in Block.forward :404-419 with per-block rates linspace(0, drop_path_rate, depth) :532-546.
+ *
+ * RANDOM NUMBERS.  Masks are never stored and never passed in: every kernel recomputes them from a counter, and the counter is made of
+ * the element's coordinates, not of a buffer layout -- every engine path draws the same mask for the same element.
+ *   generator   Philox4x32-10: multipliers 0xD2511F53 (on counter word 0), 0xCD9E8D57 (on word 2), Weyl constants 0x9E3779B9, 0xBB67AE85
+ *               added to the key words after each round.  philox(counter 0,0,0,0; key 0,0) = 6627e8d5 e169c58d bc57ac4c 9b00dbd8.
+ *   key         (seed & 0xffffffff, seed >> 32) of a 64-bit seed.
+ *   dropout     at a site of width C (768 or 3072), element (clip b, token t, column c), N = the clip's FULL token count:
+ *               e = ((b * N + t) * C + c) >> 2; counter = (e & 0xffffffff, e >> 32, site, step); output word c & 3.  One call serves
+ *               the four consecutive columns a lane holds as a float4 / 4 x 16-bit group.
+ *   drop-path   clip b: counter = (b >> 2, 0, site, step); output word b & 3.
+ *   keep rule   an element (a clip) is kept iff word >= thr, thr = (uint32) floor(p * 2^32) computed by the caller; a kept value is
+ *               multiplied by `scale` = 1 / (1 - p), a dropped one by 0.  thr = 0 keeps everything.
+ *   sites       block i: 8 i + 0 proj_drop, 8 i + 1 drop-path of the attention branch, 8 i + 2 Mlp.drop behind fc1, 8 i + 3 Mlp.drop
+ *               behind fc2, 8 i + 4 drop-path of the MLP branch; 8 * depth: pos_drop.
+ *   step        a 32-bit counter in DEVICE memory beside the seed: state = uint32 {seed lo, seed hi, step, unused}.  maest_rng_advance
+ *               copies the state into `snapshot` (uint32 [4], same layout) and then adds 1 to the step, in one launch on `stream`: a
+ *               forward calls it once, its kernels and the backward of that forward read the snapshot POINTER, never a host value --
+ *               so a captured training graph draws fresh masks at every replay.
+ * Every kernel takes the row -> (b, t) mapping as arguments: a buffer of B * n_rows_per_clip rows holds tokens 0 .. n_rows_per_clip - 1
+ * of every clip of N tokens (n_rows_per_clip = N: dense; = 2: the last block's head-token rows). */
+int maest_rng_advance(uint32_t* state, uint32_t* snapshot, void* stream);
+/* In place: x[r, c] *= keep * scale, and the same for `aux` (same shape and dtype, or NULL): the Mlp site passes gelu(fc1) and the saved
+ * gelu'(fc1), so that the MAEST_EPI_MUL dgrad yields the gradient through both; fp32 [B, N, 768]: pos_drop forward, and its backward on
+ * the gradient.  dtype MAEST_F32 / MAEST_BF16; C a multiple of 8. */
+int maest_dropout(void* x, void* aux, int dtype, int B, int N, int n_rows_per_clip, int C, uint32_t thr, float scale, int site,
+                  const uint32_t* snapshot, void* stream);
+/* maest_add_layernorm_fwd with the branch multiplier:
+ *   x_out = x + (delta * keep_e(b, t, c) * scale_e) * keep_p(b) * scale_p ; y = LN(x_out)        rows = B * n_rows_per_clip
+ * site_e < 0 switches the element part off, site_p < 0 the path part (not both).  y_dtype MAEST_F32 / MAEST_BF16. */
+int maest_drop_add_layernorm_fwd(const float* x, const void* delta, int delta_dtype, float* x_out, const float* gamma,
+                                 const float* beta, void* y, int y_dtype, float* mean, float* rstd, int B, int N,
+                                 int n_rows_per_clip, int cols, float eps, int site_e, uint32_t thr_e, float scale_e, int site_p,
+                                 uint32_t thr_p, float scale_p, const uint32_t* snapshot, void* stream);
+/* The same without the LayerNorm (the last block's fc2 branch, the head-token tail, a truncated forward). */
+int maest_drop_add(const float* x, const void* delta, int delta_dtype, float* x_out, int B, int N, int n_rows_per_clip, int cols,
+                   int site_e, uint32_t thr_e, float scale_e, int site_p, uint32_t thr_p, float scale_p, const uint32_t* snapshot,
+                   void* stream);
+/* dst = cast((src * keep_e * scale_e) * keep_p * scale_p): the gradient ENTERING a regularised branch (operand of its wgrad / dgrad
+ * GEMMs); the residual stream's fp32 gradient `src` passes unmodified, so dst must not alias it (MAEST_F32 dst: a separate buffer). */
+int maest_drop_cast(const float* src, void* dst, int dst_dtype, int B, int N, int n_rows_per_clip, int cols, int site_e,
+                    uint32_t thr_e, float scale_e, int site_p, uint32_t thr_p, float scale_p, const uint32_t* snapshot, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,7 @@ F32X3 = 2   # fp32 tensors, split-bf16 matrix products (maest_gemm_nt in_dtype /
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_MUL, EPI_ATOMIC = 0, 1, 2, 3, 4
 
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
+_U = ctypes.c_uint32
 
 # name -> argtypes, in the order of include/maest_hip.h
 SIGNATURES = {
@@ -71,6 +72,11 @@ SIGNATURES = {
     "maest_scale_f32": [_P, _L, _F, _P],
     "maest_scale_dev_f32": [_P, _L, _P, _P],
     "maest_cast_rows": [_P, _L, _P, _L, _I, _I, _I, _P],
+    "maest_rng_advance": [_P, _P, _P],
+    "maest_dropout": [_P, _P, _I, _I, _I, _I, _I, _U, _F, _I, _P, _P],
+    "maest_drop_add_layernorm_fwd": [_P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _I, _U, _F, _I, _U, _F, _P, _P],
+    "maest_drop_add": [_P, _P, _I, _P, _I, _I, _I, _I, _I, _U, _F, _I, _U, _F, _P, _P],
+    "maest_drop_cast": [_P, _P, _I, _I, _I, _I, _I, _I, _U, _F, _I, _U, _F, _P, _P],
     "maest_set_option": [_I, _I, _I],
     "maest_get_option": [_I, _P],
     "maest_set_option_thread": [_I, _I, _I],

@@ -446,6 +446,12 @@ class _Engine:
             scaled = iter(W.scaled_biases(have, EMBED_DIM))
             qkv_bias = [next(scaled) if b is not None else None for b in qkv_bias]
         fast3 = bool(self.x3_fast) and x3m and not save
+        # dropout / stochastic depth (recording train() forwards with a rate > 0; None otherwise: exactly the launches below)
+        plan = m._regulariser_plan() if save else None
+        reg = None
+        if plan is not None:
+            # (seed, step) of THIS forward, written on its stream; the state's step moves on in the same launch (csrc/regularise.hip)
+            reg = dict(snap=ops.rng_advance(m._regulariser_state(x3.device)), p=plan[0], dpr=plan[1], pos_site=8 * len(m.blocks))
         if fast3:
             w3 = W.split3([lin.weight for blk in m.blocks for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2)])
             w3 = {(i, n): w3[4 * i + j] for i in range(len(m.blocks)) for j, n in enumerate(("qkv", "proj", "fc1", "fc2"))}
@@ -459,7 +465,10 @@ class _Engine:
                                m.new_pos_embed.reshape(2, EMBED_DIM), m.freq_new_pos_embed.reshape(EMBED_DIM, -1),
                                m.time_new_pos_embed.reshape(EMBED_DIM, Tt), toffset, tok_ft, B)
         x = x.reshape(M, EMBED_DIM)
+        if reg is not None and reg["p"] > 0:       # pos_drop (models/maest.py:800)
+            ops.dropout_(x, None, B, N, N, reg["pos_site"], reg["p"], reg["snap"])
         if save:
+            ctx["reg"] = reg
             ctx["cols"] = cols
             ctx["blocks"] = []
             ctx["qs"] = qs
@@ -477,9 +486,23 @@ class _Engine:
         split_add = dt != torch.float32 and mode in (1, 2)
         split_add_fc2 = dt != torch.float32 and mode == 1
         pending = None            # delta of the previous block's fc2, to be added by this block's norm1
+        pending_reg = None        # ... and the (element, path) sites of that branch when it is regularised
         for i in range(nblocks):
             blk = m.blocks[i]
-            if pending is not None:
+            # this block's regularised sites, (site, rate) or None each (include/maest_hip.h); a block with none keeps the path below
+            br = None
+            if reg is not None and (reg["p"] > 0 or reg["dpr"][i] > 0):
+                pe, pp = reg["p"], reg["dpr"][i]
+                br = dict(elem_a=(8 * i, pe) if pe > 0 else None, path_a=(8 * i + 1, pp) if pp > 0 else None,
+                          elem_h=(8 * i + 2, pe) if pe > 0 else None, elem_m=(8 * i + 3, pe) if pe > 0 else None,
+                          path_m=(8 * i + 4, pp) if pp > 0 else None)
+            if pending is not None and pending_reg is not None:
+                r = ops.drop_add_layernorm_fwd(x, pending, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, B, N, N,
+                                               pending_reg[0], pending_reg[1], reg["snap"], save_stats=save)
+                x, ln1 = r[0], r[1]
+                mean1, rstd1 = (r[2], r[3]) if save else (None, None)
+                pending = pending_reg = None
+            elif pending is not None:
                 r = ops.add_layernorm_fwd(x, pending, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save_stats=save)
                 x, ln1 = r[0], r[1]
                 mean1, rstd1 = (r[2], r[3]) if save else (None, None)
@@ -506,11 +529,22 @@ class _Engine:
             if i == stop_block and return_self_attention:
                 # Block.forward(..., return_self_attention=True) returns attn(norm1(x)) (maest.py:414-416)
                 a = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=torch.float32)
+                if br is not None and br["elem_a"] is not None:      # proj_drop is part of Attention.forward; drop-path is not
+                    ops.dropout_(a, None, B, N, N, *br["elem_a"], reg["snap"])
                 if save:      # (the backward of this block starts at the proj GEMM: norm2 / MLP are not part of the output)
                     ctx["blocks"].append(dict(x=x_full, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, ao=ao, lse=lse, tail=False,
-                                              ao_full=ao_full, q_rows=None))
+                                              ao_full=ao_full, q_rows=None, reg=br, rpc=N))
                 return ops.embed_pool(a.reshape(B, N, EMBED_DIM)), ctx
-            if split_add:
+            rpc = HEAD_TOKENS if tail else N      # rows of a clip in this block's per-token buffers
+            if br is not None:
+                # the split form in every numeric mode: proj emits its output with the bias-only epilogue and the residual add rides, with
+                # the branch multiplier, in the LayerNorm pass that follows
+                d1 = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=dt)
+                r = ops.drop_add_layernorm_fwd(x, d1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, B, N, rpc,
+                                               br["elem_a"], br["path_a"], reg["snap"], save_stats=save)
+                x1, ln2 = r[0], r[1]
+                mean2, rstd2 = (r[2], r[3]) if save else (None, None)
+            elif split_add:
                 d1 = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=dt)
                 r = ops.add_layernorm_fwd(x, d1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save_stats=save)
                 x1, ln2 = r[0], r[1]
@@ -533,11 +567,20 @@ class _Engine:
             else:
                 g = gemm_nt(ln2, W.get(blk.mlp.fc1.weight, dt), blk.mlp.fc1.bias, out_dtype=dt, epi=ops.EPI_GELU,
                             aux_out=h)
+            if br is not None and br["elem_h"] is not None:
+                # Mlp.drop behind fc1 (models/maest.py:205), on gelu(.) and on the saved gelu'(.): the EPI_MUL dgrad then carries the mask
+                ops.dropout_(g, h, B, N, rpc, *br["elem_h"], reg["snap"])
             if save:
                 ctx["blocks"].append(dict(x=x_full, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, ao=ao, lse=lse, x1=x1,
                                           mean2=mean2, rstd2=rstd2, ln2=ln2, h=h, g=g, tail=tail, ao_full=ao_full,
-                                          q_rows=q_rows))
-            if split_add_fc2 and i + 1 < nblocks:
+                                          q_rows=q_rows, reg=br, rpc=rpc))
+            if br is not None:
+                d2 = gemm_nt(g, W.get(blk.mlp.fc2.weight, dt), blk.mlp.fc2.bias, out_dtype=dt)
+                if i + 1 < nblocks:      # the next block's norm1 carries the add
+                    pending, pending_reg, x = d2, (br["elem_m"], br["path_m"]), x1
+                else:
+                    x = ops.drop_add(x1, d2, B, N, rpc, br["elem_m"], br["path_m"], reg["snap"])
+            elif split_add_fc2 and i + 1 < nblocks:
                 pending = gemm_nt(g, W.get(blk.mlp.fc2.weight, dt), blk.mlp.fc2.bias, out_dtype=dt)
                 x = x1
             elif fast_blk and g.dtype == torch.bfloat16:     # (split rows from the fc1 epilogue)
@@ -735,14 +778,28 @@ class _Engine:
         if dt == torch.float32:
             dx_lp = dx
 
+        reg = ctx.get("reg")
+
+        def enter(d32, d_lp, elem, path, rpc):
+            """The gradient entering a residual branch: `d_lp` as it is, or -- the branch was regularised in the forward -- the stream's
+            fp32 gradient times the forward's multiplier, in a buffer of its own (the stream's gradient passes on unmodified)."""
+            if elem is None and path is None:
+                return d_lp
+            return ops.drop_cast(d32, dt, B, N, rpc, elem, path, reg["snap"])
+
         for i in reversed(range(first + 1)):
             blk, s = m.blocks[i], ctx["blocks"][i]
             p = f"blocks.{i}."
             H = blk.mlp.fc1.out_features
+            br, rpc = s.get("reg"), s.get("rpc", N)
             if attn_only and i == first:
                 # Block.forward(..., return_self_attention=True) = proj(attn(norm1 x)): no residual, no norm2 / MLP
                 dx1, dx1_lp, dres1 = dx, dx_lp, None
+                if br is not None:
+                    dx1_lp = enter(dx, dx_lp, br["elem_a"], None, rpc)
             else:
+                if br is not None:      # (before the wgrad's event: the side stream must see the masked operand)
+                    dx_lp = enter(dx, dx_lp, br["elem_m"], br["path_m"], rpc)
                 # fc2 (+ residual):  x2 = x1 + g W2^T + b2
                 wgrad(p + "mlp.fc2.weight", p + "mlp.fc2.bias", dx_lp, s["g"], EMBED_DIM, H)
                 dh = gemm_nt(dx_lp, W.get(blk.mlp.fc2.weight, dt, transposed=True), None, out_dtype=dt,
@@ -758,6 +815,8 @@ class _Engine:
                 if dt == torch.float32:
                     dx1_lp = dx1
                 dres1 = dx1
+                if br is not None:
+                    dx1_lp = enter(dx1, dx1_lp, br["elem_a"], br["path_a"], rpc)
             # proj (+ residual)
             wgrad(p + "attn.proj.weight", p + "attn.proj.bias", dx1_lp, s["ao"], EMBED_DIM, EMBED_DIM)
             wt_proj = W.get(blk.attn.proj.weight, dt, transposed=True)
@@ -786,6 +845,8 @@ class _Engine:
                 dx_lp = dx
             s.clear()  # release this block's activations
 
+        if reg is not None and reg["p"] > 0:      # pos_drop, on the gradient of the assembled tokens
+            ops.dropout_(dx, None, B, N, N, reg["pos_site"], reg["p"], reg["snap"])
         Tt = m.time_new_pos_embed.shape[-1]
         d_cls_t, d_dist_t = buf("cls_token", EMBED_DIM), buf("dist_token", EMBED_DIM)
         d_np = buf("new_pos_embed", 2, EMBED_DIM)
@@ -860,6 +921,26 @@ class _MaestFn(torch.autograd.Function):
         return (None, dx, None, None, None, *grads)
 
 
+def _check_rates(drop_rate, attn_drop_rate, drop_path_rate):
+    for name, v in (("drop_rate", drop_rate), ("attn_drop_rate", attn_drop_rate), ("drop_path_rate", drop_path_rate)):
+        if not 0.0 <= float(v) < 1.0:
+            raise ValueError(f"{name} must lie in [0, 1), got {v!r}")
+    if float(attn_drop_rate) > 0.0:
+        raise NotImplementedError("attn_drop_rate > 0: dropout on the attention probabilities inside the fused attention kernels is "
+                                  "not built (drop_rate and drop_path_rate are)")
+
+
+def regulariser_seed(initial_seed: int, rank: int = 0) -> int:
+    """The 64-bit mask seed a model derives when none was set: a pure function of torch.initial_seed() and the process's rank in the
+    default process group, so that data-parallel ranks that share a torch seed do not share masks (splitmix64 finaliser of
+    initial_seed + (rank + 1) * the 64-bit golden ratio)."""
+    m = 0xFFFFFFFFFFFFFFFF
+    z = (int(initial_seed) + (int(rank) + 1) * 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
 class MAEST(nn.Module):
     """Music Audio Efficient Spectrogram Transformer (reference class: models/maest.py:423-939)."""
 
@@ -867,8 +948,9 @@ class MAEST(nn.Module):
                  s_patchout_f_interleaved=0, s_patchout_t_indices=(), s_patchout_t_interleaved=0,
                  img_size=(96, 625), patch_size=16, stride=10, in_chans=1, num_classes=400, embed_dim=768,
                  depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True, distilled=True, distilled_type="mean",
-                 precision="auto", _skip_init: bool = False):
+                 precision="auto", drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, _skip_init: bool = False):
         super().__init__()
+        _check_rates(drop_rate, attn_drop_rate, drop_path_rate)
         self._skip_init = bool(_skip_init)      # clone_weights(): the twin's parameters are copies, not draws
         self._init_kwargs = dict(u_patchout=u_patchout, s_patchout_t=s_patchout_t, s_patchout_f=s_patchout_f,
                                  s_patchout_f_indices=s_patchout_f_indices,
@@ -878,7 +960,8 @@ class MAEST(nn.Module):
                                  patch_size=patch_size, stride=stride, in_chans=in_chans, num_classes=num_classes,
                                  embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
                                  qkv_bias=qkv_bias, distilled=distilled, distilled_type=distilled_type,
-                                 precision=precision)
+                                 precision=precision, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
+                                 drop_path_rate=drop_path_rate)
         if embed_dim != EMBED_DIM or num_heads != NUM_HEADS or patch_size != PATCH or in_chans != 1:
             raise NotImplementedError("maest_amd kernels are specialised for the MAEST geometry: "
                                       "embed_dim=768, 12 heads x 64, 16x16 patches, mono input")
@@ -897,6 +980,12 @@ class MAEST(nn.Module):
         self.num_tokens = 2
         self.distilled_type = distilled_type
         self.precision = precision
+        # regularisers of the training step (models/maest.py:452-454): plain attributes, read at every recording train() forward
+        self.drop_rate = float(drop_rate)
+        self.attn_drop_rate = float(attn_drop_rate)
+        self.drop_path_rate = float(drop_path_rate)
+        self._reg_seed = None        # set_regulariser_seed(), else derived at the first regularised forward
+        self._reg_state = {}         # {device: int32 [4] = seed lo, seed hi, step, 0} (include/maest_hip.h), not a registered buffer
         if num_classes == 400:
             self.labels = discogs_400labels
         elif num_classes == 519:
@@ -938,11 +1027,12 @@ class MAEST(nn.Module):
         # configuration changed after construction travels too (patchout switched off for evaluation, numeric mode, engine
         # switches) -- run-time state does not, and neither does graph replay: a twin (SWA average, teacher) captures graphs,
         # with their private memory pools, only when its owner calls enable_hip_graph() on it
-        for k in ("precision", "u_patchout", "s_patchout_t", "s_patchout_f", "s_patchout_f_indices",
+        for k in ("precision", "drop_rate", "attn_drop_rate", "drop_path_rate", "u_patchout", "s_patchout_t", "s_patchout_f", "s_patchout_f_indices",
                   "s_patchout_f_interleaved", "s_patchout_t_indices", "s_patchout_t_interleaved"):
             setattr(twin, k, getattr(self, k))
         twin._engine.head_tail = self._engine.head_tail
         twin._engine.overlap_wgrad = self._engine.overlap_wgrad
+        twin._reg_seed = self._reg_seed      # (the twin's step counter starts at 0 on its own device state)
         dev = next(self.parameters()).device
         twin.to(dev)
         with torch.no_grad():
@@ -958,6 +1048,37 @@ class MAEST(nn.Module):
         twin = self.clone_weights()
         memo[id(self)] = twin
         return twin
+
+    # ---- regularisers: dropout and stochastic depth ----------------------------------------------
+    @property
+    def drop_path_rates(self):
+        """Drop-path rate of every block: linspace(0, drop_path_rate, depth), as the reference computes it (models/maest.py:534-536)."""
+        return [float(v) for v in torch.linspace(0, self.drop_path_rate, len(self.blocks))]
+
+    def set_regulariser_seed(self, seed: int):
+        """Seed of the dropout / drop-path masks (include/maest_hip.h: the Philox key); the step counter restarts at 0.  Without a call
+        the seed is regulariser_seed(torch.initial_seed(), rank), taken once at the first regularised forward."""
+        self._reg_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        for dev, st in self._reg_state.items():      # in place: a captured training graph holds this buffer
+            st.copy_(ops.rng_state(self._reg_seed, "cpu"))
+        return self
+
+    def _regulariser_state(self, dev):
+        st = self._reg_state.get(str(dev))
+        if st is None:
+            if self._reg_seed is None:
+                import torch.distributed as dist
+                rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+                self._reg_seed = regulariser_seed(torch.initial_seed(), rank)
+            st = self._reg_state[str(dev)] = ops.rng_state(self._reg_seed, dev)
+        return st
+
+    def _regulariser_plan(self):
+        """What a recording train() forward applies: None (every rate 0: today's launches), else (drop_rate, per-block drop-path rates)."""
+        _check_rates(self.drop_rate, self.attn_drop_rate, self.drop_path_rate)
+        if not self.training or (self.drop_rate == 0.0 and self.drop_path_rate == 0.0):
+            return None
+        return float(self.drop_rate), self.drop_path_rates
 
     # ---- reference API odds and ends --------------------------------------------------------
     def init_weights(self, mode=""):
@@ -1286,8 +1407,11 @@ class MAEST(nn.Module):
         stripes = kw.get("stripes")
         dyn = {"tok_ft": kw["tok_ft"], "perm": kw["perm"], "lam": kw["lam"],
                "t_stripes": None if stripes is None else stripes[0], "f_stripes": None if stripes is None else stripes[1]}
+        plan = self._regulariser_plan()
+        if plan is not None:
+            self._regulariser_state(x3.device)      # (made outside any capture: the graph holds it as a static buffer)
         key = ("train", tuple(x3.shape), x3.dtype, dt, self.precision, kw["x3m"], kw["toffset"], str(x3.device), bool(eng.head_tail),
-               bool(self.training), tuple((k, None if v is None else tuple(v.shape)) for k, v in dyn.items()))
+               bool(self.training), None if plan is None else (plan[0], self.drop_path_rate), tuple((k, None if v is None else tuple(v.shape)) for k, v in dyn.items()))
         st = self._graphs.get(key)
         if st is None:
             if len(self._graphs) >= 8:
@@ -1354,9 +1478,10 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
               s_patchout_f: int = 0, s_patchout_f_indices: tuple = (), s_patchout_f_interleaved: int = 0,
               s_patchout_t_indices: tuple = (), s_patchout_t_interleaved: int = 0, distilled_type: str = "mean",
               checkpoint: str = None, checkpoint_swa_weigts: bool = True, checkpoint_discard_head: bool = False,
-              precision: str = "auto"):
+              precision: str = "auto", *, drop_rate: float = 0.0, drop_path_rate: float = 0.0):
     """Same signature and semantics as the reference factory (models/maest.py:1467-1569), plus
-    ``precision`` (see the module docstring).  Returns the model in train mode, like the reference."""
+    ``precision`` (see the module docstring) and the keyword-only ``drop_rate`` / ``drop_path_rate`` of the MAEST constructor.
+    Returns the model in train mode, like the reference."""
     if arch not in _ARCH_DEFAULT_T:
         raise NotImplementedError(f"model {arch} not implemented")
     if pretrained:
@@ -1377,7 +1502,7 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
                   s_patchout_t_indices=s_patchout_t_indices, s_patchout_t_interleaved=s_patchout_t_interleaved,
                   img_size=(input_f, input_t), patch_size=16, stride=(stride_f, stride_t), in_chans=in_channels,
                   num_classes=n_classes, embed_dim=768, depth=12, num_heads=12, distilled=True,
-                  distilled_type=distilled_type, precision=precision)
+                  distilled_type=distilled_type, precision=precision, drop_rate=drop_rate, drop_path_rate=drop_path_rate)
     if checkpoint:
         state_dict = torch.load(checkpoint, map_location="cpu")["state_dict"]
         replace_str = "net_swa." if checkpoint_swa_weigts else ""

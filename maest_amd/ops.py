@@ -278,6 +278,85 @@ def add_layernorm_fwd(x: torch.Tensor, delta: torch.Tensor, gamma, beta, eps: fl
     return (x_new, y, mean, rstd) if save_stats else (x_new, y)
 
 
+# ------------------------------------------------------------------------------------ regularisers (csrc/regularise.hip)
+def drop_threshold(p: float) -> int:
+    """The uint32 keep threshold of rate p (include/maest_hip.h: kept iff word >= thr)."""
+    return int(p * 4294967296.0)
+
+
+def drop_scale(p: float) -> float:
+    """1 / (1 - p) as the fp32 value the kernels multiply kept elements by."""
+    return float(np.float32(1.0) / np.float32(1.0 - p))
+
+
+def _site_args(part):
+    """(site, rate) | None -> the (site, thr, scale) launch arguments of one part of a branch multiplier (site -1: off)."""
+    if part is None:
+        return -1, 0, 1.0
+    site, p = part
+    return int(site), drop_threshold(p), drop_scale(p)
+
+
+def rng_state(seed: int, device, step: int = 0) -> torch.Tensor:
+    """The generator state of include/maest_hip.h as an int32 [4] tensor: {seed lo, seed hi, step, 0} (bit patterns of uint32)."""
+    words = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, step & 0xFFFFFFFF, 0], dtype=np.uint32).view(np.int32)
+    return torch.from_numpy(words.copy()).to(device)
+
+
+def rng_advance(state: torch.Tensor) -> torch.Tensor:
+    """-> a fresh snapshot (int32 [4]) of `state`; the state's step then moves on by one (one launch on the current stream)."""
+    _chk(state)
+    assert state.dtype == torch.int32 and state.numel() == 4
+    snap = torch.empty(4, dtype=torch.int32, device=state.device)
+    _timed_call("maest_rng_advance", 0.0, _p(state), _p(snap), _s(state))
+    return snap
+
+
+def dropout_(x: torch.Tensor, aux: Optional[torch.Tensor], B: int, N: int, rows_per_clip: int, site: int, p: float, snap: torch.Tensor):
+    """In place: x (and aux) [B * rows_per_clip, C] *= keep / (1 - p), the mask of `site` at the step of `snap`."""
+    _chk(x, aux, snap)
+    assert x.dim() == 2 and x.shape[0] == B * rows_per_clip and x.dtype in DT
+    assert aux is None or (aux.shape == x.shape and aux.dtype == x.dtype)
+    _timed_call("maest_dropout", 0.0, _p(x), _p(aux), DT[x.dtype], B, N, rows_per_clip, int(x.shape[1]), drop_threshold(p), drop_scale(p),
+                int(site), _p(snap), _s(x))
+    return x
+
+
+def drop_add_layernorm_fwd(x, delta, gamma, beta, eps: float, out_dtype, B: int, N: int, rows_per_clip: int, elem, path, snap,
+                           save_stats=False):
+    """add_layernorm_fwd with the branch multiplier: elem / path = (site, rate) or None.  -> (x_new fp32, y[, mean, rstd])."""
+    _chk(x, delta, gamma, beta, snap)
+    assert x.dtype == torch.float32 and x.dim() == 2 and delta.shape == x.shape and x.shape[0] == B * rows_per_clip
+    rows, cols = x.shape
+    x_new = torch.empty_like(x)
+    y = torch.empty((rows, cols), dtype=out_dtype, device=x.device)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
+    _timed_call("maest_drop_add_layernorm_fwd", 0.0, _p(x), _p(delta), DT[delta.dtype], _p(x_new), _p(gamma), _p(beta), _p(y), DT[out_dtype],
+                _p(mean), _p(rstd), B, N, rows_per_clip, cols, eps, *_site_args(elem), *_site_args(path), _p(snap), _s(x))
+    return (x_new, y, mean, rstd) if save_stats else (x_new, y)
+
+
+def drop_add(x, delta, B: int, N: int, rows_per_clip: int, elem, path, snap):
+    """x fp32 + delta * multiplier -> x_new fp32 (drop_add_layernorm_fwd without the LayerNorm)."""
+    _chk(x, delta, snap)
+    assert x.dtype == torch.float32 and x.dim() == 2 and delta.shape == x.shape and x.shape[0] == B * rows_per_clip
+    x_new = torch.empty_like(x)
+    _timed_call("maest_drop_add", 0.0, _p(x), _p(delta), DT[delta.dtype], _p(x_new), B, N, rows_per_clip, int(x.shape[1]),
+                *_site_args(elem), *_site_args(path), _p(snap), _s(x))
+    return x_new
+
+
+def drop_cast(src, dtype, B: int, N: int, rows_per_clip: int, elem, path, snap):
+    """fp32 gradient of the residual stream -> the gradient entering a regularised branch, in `dtype` (a new buffer; src is left as is)."""
+    _chk(src, snap)
+    assert src.dtype == torch.float32 and src.dim() == 2 and src.shape[0] == B * rows_per_clip
+    dst = torch.empty(src.shape, dtype=dtype, device=src.device)
+    _timed_call("maest_drop_cast", 0.0, _p(src), _p(dst), DT[dtype], B, N, rows_per_clip, int(src.shape[1]),
+                *_site_args(elem), *_site_args(path), _p(snap), _s(src))
+    return dst
+
+
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, lp_dtype=None, want_fp32=True, head_tokens=None):
     """-> (dx fp32 or None, dx in lp_dtype or None); dgamma/dbeta accumulated in place.
     head_tokens = (n_tok, n_head): `dres` is compact, [rows / n_tok * n_head, 768] -- the residual gradient of the
