@@ -18,6 +18,16 @@
  *    fp32 accumulate, "perf mode").  The residual stream, LayerNorm statistics, softmax statistics,
  *    logits and all parameter gradients are fp32 in both modes.
  *  - No torch types, no C++ types: plain pointers and integers only.
+ *  - Memory contract (pinned by tests/guard.py, which runs every entry point with each argument between NaN-filled bands):
+ *      * an entry point reads and writes only [ptr, ptr + extent) of each argument, the extent being what its sizes and its leading
+ *        dimension say (rows x ld elements, the last row only as wide as the logical row); a `const` argument is never written, and
+ *        an output or workspace is never read before the call itself has written it (ACCUMULATED outputs excepted: the caller
+ *        initialises those);
+ *      * rows past a ragged edge (a partial last tile of M, N, K or of a clip's tokens) are re-read from the last valid row or
+ *        zero-filled on chip -- never fetched from beyond it, not even to be multiplied by zero: the neighbour's memory may hold inf / NaN;
+ *      * pad columns of a leading dimension wider than the logical row are left alone unless the entry says otherwise
+ *        (maest_transpose and maest_cast_rows zero them); rows an entry declares "not written" / "untouched" keep their bytes;
+ *      * a workspace of exactly the documented minimum size is enough.
  */
 #ifndef MAEST_HIP_H
 #define MAEST_HIP_H

@@ -82,6 +82,32 @@ SIGNATURES = {
     "maest_set_option_thread": [_I, _I, _I],
     "maest_kernel_forms": [_P],
 }
+# name -> positions (in SIGNATURES[name]) of the DEVICE pointer arguments the entry point may write: the ones include/maest_hip.h does not
+# declare const (for the two entries that take host arrays of device pointers: the arrays whose elements point at written memory).
+# Every other device pointer is only read.  tests/test_guard_cpu.py checks the table against the header; tests/guard.py relies on it.
+WRITTEN = {
+    "maest_gemm_nt": (5, 14), "maest_gemm_nt_rowdot": (5, 14), "maest_gemm_tn": (5, 10), "maest_gemm_tn_ws": (5, 10, 12),
+    "maest_transpose": (2,), "maest_cast_weights": (1, 2), "maest_cast_weights_multi": (2, 3),
+    "maest_layernorm_fwd": (4, 7, 8), "maest_add_layernorm_fwd": (3, 6, 8, 9), "maest_layernorm_bwd": (9, 10, 12, 13),
+    "maest_attn_fwd": (1, 2), "maest_attn_bwd": (4, 5), "maest_attn_fwd_rows": (1, 2), "maest_attn_bwd_rows": (4, 5),
+    "maest_layernorm_bwd_headres": (9, 10, 12, 13), "maest_gather_head_rows": (5,), "maest_scatter_head_rows": (6,),
+    "maest_patch_im2col": (13,), "maest_patch_im2col_strided": (15,), "maest_patch_im2col_bwd": (15, 17),
+    "maest_token_assemble": (12,), "maest_token_assemble_bwd": (7, 9, 10, 11, 12, 13),
+    "maest_head_pool_fwd": (6, 7, 8, 9, 10), "maest_head_pool_bwd": (9, 10, 11), "maest_embed_pool": (3,), "maest_embed_pool_bwd": (3, 4),
+    "maest_bce_logits": (7, 8), "maest_sigmoid_mean": (3,), "maest_colsum": (5,), "maest_spec_mask": (0,),
+    "maest_swa_update_multi": (1,), "maest_affine_f32": (0,), "maest_augment_mel": (15,), "maest_augment_mel_bwd": (17, 19),
+    "maest_melfile_assemble": (9,), "maest_logmel": (12,), "maest_logmel_bwd": (15, 17), "maest_logmel_rows_f16": (13,),
+    "maest_resample": (12,), "maest_scale_f32": (0,), "maest_scale_dev_f32": (0,), "maest_cast_rows": (2,),
+    "maest_rng_advance": (0, 1), "maest_dropout": (0, 1), "maest_drop_add_layernorm_fwd": (3, 6, 8, 9), "maest_drop_add": (3,),
+    "maest_drop_cast": (1,),
+}
+# name -> {position: kind} of the pointer arguments that are HOST memory: results written through a pointer, and the arrays (of device
+# pointers, of sizes) of the two multi-tensor entries.  Every other pointer but the last one (the stream) is a device pointer.
+HOST_POINTERS = {
+    "maest_gemm_tn_workspace_bytes": {5: "result"}, "maest_get_option": {1: "result"}, "maest_kernel_forms": {0: "result"},
+    "maest_cast_weights_multi": {1: "device pointers", 2: "device pointers", 3: "device pointers", 4: "sizes", 5: "sizes", 6: "sizes"},
+    "maest_swa_update_multi": {1: "device pointers", 2: "device pointers", 3: "sizes"},
+}
 FORM_GEMM_NT_OW, FORM_GEMM_TN_OW, FORM_ATTN_FWD_PW = 1, 2, 4
 
 ABI_VERSION = 9

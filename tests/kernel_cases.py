@@ -978,3 +978,186 @@ def case_nonfinite(dev, M=144, N=200, K=128, B=2, Ntok=40, rows=11, gemm_forms=(
     bad_c[11] = True
     _finite_except(dg, bad_c, "layernorm_bwd dgamma")
     _finite_except(db, bad_c, "layernorm_bwd dbeta")
+
+
+# ------------------------------------------------------------------------------------- the memory contract (include/maest_hip.h, "Conventions")
+# These cases run inside `with tests.guard.guarded():` only: the buffers ops allocates then come back filled with the guard's pattern, so
+# "not written" is visible bit for bit, and every call is checked for accesses outside its operands.  No tolerance anywhere: bit patterns.
+def _guard():
+    from tests import guard
+    assert guard.guarded._active is not None, "the memory-contract cases need tests.guard.guarded()"
+    return guard
+
+
+def case_contract_attention_rows(dev, dtype, B, N, seed=26):
+    """maest_attn_fwd_rows with q_rows = 2: rows >= 32 of `out` and `lse` of EVERY clip are not written; the rows of the 32-row tile are.
+    maest_scatter_head_rows: rows >= n_pad of every clip untouched, rows [n_head, n_pad) exactly zero, for n_pad in {2, 32, N}."""
+    G = _guard()
+    qkv = lp(rnd((B * N, 2304), seed, 1.0), dtype).to(dev)
+    out, lse = ops.attn_fwd(qkv, B, N, 0.125, save_lse=True, q_rows=2)
+    nv = min(32, N)
+    o3 = out.reshape(B, N, 768)
+    assert bool(G.untouched(o3[:, nv:]).all()), "attn_fwd_rows wrote output rows beyond the 32-row tile of the head tokens"
+    assert bool(G.untouched(lse[:, :, nv:]).all()), "attn_fwd_rows wrote lse beyond the 32-row tile of the head tokens"
+    assert not bool(G.untouched(o3[:, :nv]).any()) and not bool(G.untouched(lse[:, :, :nv]).any()), "rows of the head tokens' tile left unwritten"
+    assert bool(torch.isfinite(f32(o3[:, :nv])).all()) and bool(torch.isfinite(lse[:, :, :nv]).all())
+    comp = lp(rnd((B * 2, 768), seed + 1), dtype).to(dev)
+    for n_pad in sorted({2, nv, N}):
+        back = ops.scatter_head_rows(comp, B, N, 2, n_pad).reshape(B, N, 768)
+        assert torch.equal(back[:, :2], comp.reshape(B, 2, 768)), f"scatter_head_rows n_pad={n_pad}: head rows"
+        assert not bool(back[:, 2:n_pad].contiguous().view(torch.int16 if dtype != torch.float32 else torch.int32).any()), f"n_pad={n_pad}: rows [2, n_pad) must be zero"
+        assert bool(G.untouched(back[:, n_pad:]).all()), f"scatter_head_rows n_pad={n_pad}: rows >= n_pad must stay untouched"
+
+
+def case_contract_fully_written(dev, B=3, N=7):
+    """maest_head_pool_bwd: every row >= 2 of dx exactly zero (written, not left); maest_embed_pool_bwd and maest_patch_im2col_bwd: fully
+    written, no fill pattern left (the latter with its int32 workspace at exactly the documented minimum, which ops allocates)."""
+    G = _guard()
+    x = rnd((B, N, 768), 50, 1.5).to(dev)
+    g, b = (1.0 + rnd((768,), 51, 0.1)).to(dev), rnd((768,), 52, 0.1).to(dev)
+    cls, dist, feat, mean, rstd = ops.head_pool_fwd(x, g, b, 1e-6, save_stats=True)
+    for t in (cls, dist, feat, mean, rstd):
+        assert not bool(G.untouched(t).any()), "head_pool_fwd left an output element unwritten"
+    dg, db = torch.zeros(768, device=dev), torch.zeros(768, device=dev)
+    dx = ops.head_pool_bwd(rnd((B, 768), 53).to(dev), rnd((B, 768), 54).to(dev), rnd((B, 768), 55).to(dev), x, g, mean, rstd, dg, db)
+    assert not bool(dx[:, 2:].contiguous().view(torch.int32).any()), "head_pool_bwd: rows >= 2 of dx must be exactly zero"
+    assert not bool(G.untouched(dx[:, :2]).any())
+    dxe, lpe = ops.embed_pool_bwd(rnd((B, 3 * 768), 56).to(dev), N, lp_dtype=torch.bfloat16)
+    assert not bool(G.untouched(dxe).any()) and not bool(G.untouched(lpe).any()), "embed_pool_bwd left rows unwritten"
+    Fdim, T, stride = 42, 46, (10, 10)
+    Fp, Tp = (Fdim - 16) // 10 + 1, (T - 16) // 10 + 1
+    tok = torch.tensor([(f, t) for f in range(Fp) for t in range(Tp) if (f, t) != (1, 2)], dtype=torch.int32).to(dev)      # one patch dropped
+    perm = torch.tensor([2, 0, 1], dtype=torch.int32).to(dev)
+    lam = torch.tensor([0.7, 0.35, 0.9]).to(dev)
+    for dt, xdt in ((torch.float32, torch.float32), (torch.bfloat16, torch.float16)):
+        dcols = lp(rnd((3 * tok.shape[0], 256), 57), dt).to(dev)
+        for mix in (False, True):
+            dxp = ops.patch_im2col_bwd(dcols, (3, Fdim, T), xdt, tok, perm=perm if mix else None, lam=lam if mix else None, stride=stride)
+            assert not bool(G.untouched(dxp).any()), f"patch_im2col_bwd left samples unwritten ({dt}, mixup {mix})"
+            assert bool(torch.isfinite(dxp.float()).all())
+
+
+def case_contract_padded_leading_dims(dev, dtype, M, N, K, tn_K=None, pad=64):
+    """Leading dimensions wider than the logical row: the pad columns of an output are bitwise untouched (or exactly zero where the header
+    says zero), pad columns of an INPUT -- here holding the NaN pattern -- never reach a result; each result is bit-equal to the dense call."""
+    G = _guard()
+    it = torch.int32 if dtype == torch.float32 else torch.int16
+
+    def wide(rows, cols, dt, src=None):
+        w = G.fill_pattern_(torch.empty((rows, cols + pad), dtype=dt, device=dev))
+        if src is not None:
+            w[:, :cols] = src
+        return w
+
+    a, b = lp(rnd((M, K), 70), dtype).to(dev), lp(rnd((N, K), 71) * 0.1, dtype).to(dev)
+    bias = rnd((N,), 72).to(dev)
+    # outputs as column slices (ldc = ld_aux = N + pad)
+    aux_d = torch.empty((M, N), dtype=dtype, device=dev)
+    c_d = ops.gemm_nt(a, b, bias, out_dtype=dtype, epi=ops.EPI_GELU, aux_out=aux_d)
+    cw, auxw = wide(M, N, dtype), wide(M, N, dtype)
+    ops.gemm_nt(a, b, bias, out=cw[:, :N], epi=ops.EPI_GELU, aux_out=auxw[:, :N])
+    assert torch.equal(cw[:, :N].contiguous().view(it), c_d.view(it)), "gemm_nt into a column slice differs from the dense call"
+    assert torch.equal(auxw[:, :N].contiguous().view(it), aux_d.view(it)), "gemm_nt aux_out into a column slice differs from the dense call"
+    assert bool(G.untouched(cw[:, N:]).all()) and bool(G.untouched(auxw[:, N:]).all()), "gemm_nt wrote pad columns of C / aux_out"
+    # operands as column slices (lda = ldb = K + pad), NaN pattern in the pad
+    c_f = ops.gemm_nt(a, b, bias, out_dtype=torch.float32)
+    c_s = ops.gemm_nt(wide(M, K, dtype, a)[:, :K], wide(N, K, dtype, b)[:, :K], bias, out_dtype=torch.float32)
+    assert torch.equal(c_s.view(torch.int32), c_f.view(torch.int32)), "gemm_nt on column-slice operands differs from the dense call"
+    # wgrad with ldc > N
+    Kt = tn_K or M
+    ta, tb = lp(rnd((Kt, 136), 73), dtype).to(dev), lp(rnd((Kt, 200), 74), dtype).to(dev)
+    o_d = torch.zeros((136, 200), dtype=torch.float32, device=dev)
+    ops.gemm_tn(ta, tb, o_d, split_k=1)
+    ow = wide(136, 200, torch.float32, 0.0)
+    ops.gemm_tn(ta, tb, ow[:, :200], split_k=1)
+    assert torch.equal(ow[:, :200].contiguous().view(torch.int32), o_d.view(torch.int32)), "gemm_tn into a column slice differs from the dense call"
+    assert bool(G.untouched(ow[:, 200:]).all()), "gemm_tn wrote pad columns of C"
+    # cast_rows / transpose: pad columns of dst are ZERO by the header
+    src = rnd((70, 130), 75).to(dev)
+    r = ops.cast_rows(src, dtype, ld_dst=192)
+    assert torch.equal(r[:, :130].contiguous().view(it), lp(src.cpu(), dtype).to(dev).view(it)) and not bool(r[:, 130:].contiguous().view(it).any()), "cast_rows pad"
+    s16 = lp(src.cpu(), dtype).to(dev)
+    t = ops.transpose(s16, 128)
+    assert torch.equal(t[:, :70].contiguous().view(it), s16.t().contiguous().view(it)) and not bool(t[:, 70:].contiguous().view(it).any()), "transpose pad"
+
+
+def case_contract_ragged_tables(dev):
+    """maest_logmel_rows_f16 / maest_resample: the last track ends exactly at the end of the input buffer, its rows / outputs exactly at the
+    end of the output; then an n_blocks that over-covers the table, and an output with rows no track covers: nothing outside the tracks'
+    rows changes, and the covered rows equal the first call's bit for bit."""
+    G = _guard()
+    from maest_amd import mel_extractor as X
+    from maest_amd.melspectrogram import MelConstants
+    consts = MelConstants(dev, 16000, 512, 96, norm_mean=0.0, norm_std=0.5)
+    lens = [300, 64 * 256 + 77, 2563]                      # offsets 0, 320 (64-sample grid), then 3 past the grid: the element-wise fetch
+    offs = [0, 320, 320 + 16512 + 3]
+    buf = torch.zeros(offs[-1] + lens[-1])                  # the last track ends exactly at the buffer's end
+    for o, n, s in zip(offs, lens, (1, 2, 3)):
+        buf[o:o + n] = rnd((n,), 500 + s, 0.3)
+    counts = [1 + n // 256 for n in lens]
+    r0 = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+    tab = torch.tensor([[o, n, 0, c, r] for o, n, c, r in zip(offs, lens, counts, r0)], dtype=torch.int64).to(dev)
+    bs = torch.from_numpy(X._blocks(counts, 64)).to(dev)
+    total = int(sum(counts))
+    rows = ops.logmel_rows_f16(buf.to(dev), tab, bs, int(bs[-1]), total, consts)
+    assert not bool(G.untouched(rows).any()) and bool(torch.isfinite(rows.float()).all())
+    more = ops.logmel_rows_f16(buf.to(dev), tab, bs, int(bs[-1]) + 3, total + 5, consts)          # blocks past the table, rows past the tracks
+    assert torch.equal(more[:total].view(torch.int16), rows.view(torch.int16)) and bool(G.untouched(more[total:]).all())
+    # resampler 44.1 kHz -> 16 kHz (160 / 441)
+    filt = X._filter(44100, torch.device(dev))
+    ilen = [4417, 1000, 37]
+    olen = [filt.out_length(n) for n in ilen]
+    x = rnd((sum(ilen),), 600, 0.3).to(dev)
+    ioff = np.concatenate([[0], np.cumsum(ilen)[:-1]]).astype(np.int64)
+    ooff = np.concatenate([[0], np.cumsum(olen)[:-1]]).astype(np.int64)
+    rtab = torch.from_numpy(np.stack([ioff, np.asarray(ilen, np.int64), ooff, np.asarray(olen, np.int64)], 1)).to(dev)
+    rbs = torch.from_numpy(X._blocks(olen, 256)).to(dev)
+    out = G.fill_pattern_(torch.empty(sum(olen), dtype=torch.float32, device=dev))
+    ops.resample(x, rtab, rbs, int(rbs[-1]), filt, out)
+    assert not bool(G.untouched(out).any()) and bool(torch.isfinite(out).all())
+    out2 = G.fill_pattern_(torch.empty(sum(olen) + 7, dtype=torch.float32, device=dev))
+    ops.resample(x, rtab, rbs, int(rbs[-1]) + 2, filt, out2)
+    assert torch.equal(out2[:sum(olen)], out) and bool(G.untouched(out2[sum(olen):]).all())
+
+
+def case_entries_without_a_wrapper(dev, dtype=torch.bfloat16, B=2, N=40):
+    """The entry points ops reaches only through a more general sibling -- maest_gemm_tn (maest_gemm_tn_ws), maest_attn_fwd / maest_attn_bwd
+    (the _rows forms), maest_layernorm_bwd (_headres), maest_patch_im2col (_strided) -- called directly, bit for bit against the sibling;
+    and the two in-place scalers."""
+    p, s, F32c, code = ops._p, ops._s, ops.DT[torch.float32], ops.DT[dtype]
+    new = lambda *shape, dt=torch.float32: ops.torch.empty(shape, dtype=dt, device=dev)      # (ops.torch: filled by an active guard)
+    ta, tb = lp(rnd((150, 136), 80), dtype).to(dev), lp(rnd((150, 200), 81), dtype).to(dev)
+    want, cs_want = torch.zeros((136, 200), device=dev), torch.zeros(136, device=dev)
+    ops.gemm_tn(ta, tb, want, colsum=cs_want, split_k=1)
+    got, cs = torch.zeros((136, 200), device=dev), torch.zeros(136, device=dev)
+    ops.call("maest_gemm_tn", p(ta), 136, p(tb), 200, code, p(got), 200, 136, 200, 150, p(cs), 1, s(ta))
+    assert torch.equal(got, want) and torch.equal(cs, cs_want), "maest_gemm_tn differs from maest_gemm_tn_ws without a workspace"
+    qkv = lp(rnd((B * N, 2304), 82), dtype).to(dev)
+    o_w, lse_w = ops.attn_fwd(qkv, B, N, 0.125, save_lse=True)
+    o, lse = new(B * N, 768, dt=dtype), new(B, 12, N)
+    ops.call("maest_attn_fwd", p(qkv), p(o), p(lse), B, N, code, 0.125, s(qkv))
+    assert torch.equal(o.view(torch.int16), o_w.view(torch.int16)) and torch.equal(lse, lse_w), "maest_attn_fwd differs from maest_attn_fwd_rows(q_rows = N)"
+    dout = lp(rnd((B * N, 768), 83), dtype).to(dev)
+    d_w = ops.attn_bwd(qkv, o_w, dout, lse_w, B, N, 0.125)
+    d, delta = new(B * N, 2304, dt=dtype), new(B, 12, N)
+    ops.call("maest_attn_bwd", p(qkv), p(o_w), p(dout), p(lse_w), p(delta), p(d), B, N, code, 0.125, s(qkv))
+    assert torch.equal(d.view(torch.int16), d_w.view(torch.int16)), "maest_attn_bwd differs from maest_attn_bwd_rows(q_rows = N)"
+    rows = 11
+    x, g, b = (rnd((rows, 768), 84, 2.0) + 0.3).to(dev), (1.0 + rnd((768,), 85, 0.1)).to(dev), rnd((768,), 86, 0.1).to(dev)
+    _, mean, rstd = ops.layernorm_fwd(x, g, b, 1e-6, dtype, save_stats=True)
+    dy, dres = lp(rnd((rows, 768), 87), dtype).to(dev), rnd((rows, 768), 88).to(dev)
+    dg_w, db_w = torch.zeros(768, device=dev), torch.zeros(768, device=dev)
+    dx_w, lp_w = ops.layernorm_bwd(dy, x, g, mean, rstd, dres, dg_w, db_w, lp_dtype=dtype)
+    dg, db, dx, dxl = torch.zeros(768, device=dev), torch.zeros(768, device=dev), new(rows, 768), new(rows, 768, dt=dtype)
+    ops.call("maest_layernorm_bwd", p(dy), 768, code, p(x), 768, p(g), p(mean), p(rstd), p(dres), p(dx), p(dxl), code, p(dg), p(db), rows, 768, s(x))
+    assert torch.equal(dx, dx_w) and torch.equal(dxl.view(torch.int16), lp_w.view(torch.int16)), "maest_layernorm_bwd differs from the _headres form with n_head = 0"
+    close(dg, dg_w, 1e-4, 1e-4 * math.sqrt(rows), "maest_layernorm_bwd dgamma (atomics)")
+    xm = rnd((2, 96, 66), 89).to(dev)
+    tok = torch.stack(torch.meshgrid(torch.arange(9), torch.arange(6), indexing="ij"), -1).reshape(-1, 2).to(torch.int32).contiguous().to(dev)
+    c_w = ops.patch_im2col(xm, tok, dtype)
+    c = new(2 * 54, 256, dt=dtype)
+    ops.call("maest_patch_im2col", p(xm), F32c, 2, 96, 66, None, None, p(tok), 54, None, 0, None, 0, p(c), code, s(xm))
+    assert torch.equal(c.view(torch.int16), c_w.view(torch.int16)), "maest_patch_im2col differs from the strided form at (10, 10)"
+    v = rnd((1000,), 90)
+    close(ops.affine_(v.clone().to(dev), 4.5, 5.0), (v + 4.5) / 5.0, 1e-6, 1e-7, "affine")
+    close(ops.scale_dev_(v.clone().to(dev), torch.tensor([0.25]).to(dev)), v * 0.25, 0, 0, "scale by a device factor")
