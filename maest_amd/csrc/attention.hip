@@ -265,9 +265,6 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
     float m_run = NEG_BIG, l_run = 0.0f;
     const float c2 = sc_c2;
 
-#ifndef MAEST_ABLATE_FWD
-#define MAEST_ABLATE_FWD 0     // timing experiments only (scratch/attn_ablate.sh fwd; results wrong on purpose): bit 0 no softmax math,
-#endif                         // 1 no P V products, 2 no S products, 3 no K / V tile refills, 4 no O store
     const int ntiles = (N + 63) / 64;
     TileRegs<T> kr, vr;
     tile_load<T>(kr, kbase, QKV_LD, 0, N, tid);
@@ -278,7 +275,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
     for (int kt = 0; kt < ntiles; ++kt) {
         const char* k_lds = smem + (kt & 1) * 2 * C::TILE;
         const char* v_lds = k_lds + C::TILE;
-        const bool more = kt + 1 < ntiles && !(MAEST_ABLATE_FWD & 8);
+        const bool more = kt + 1 < ntiles;
         if (more) {
             tile_load<T>(kr, kbase, QKV_LD, (kt + 1) * 64, N, tid);
             tile_load<T>(vr, vbase, QKV_LD, (kt + 1) * 64, N, tid);
@@ -289,8 +286,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s[kb][r] = (MAEST_ABLATE_FWD & 4) ? (float)(lane + r) : 0.0f;
-            if (!(MAEST_ABLATE_FWD & 4)) mma_rows<T, X3>(s[kb], k_lds, kb * 32, lane, qf);
+            for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
+            mma_rows<T, X3>(s[kb], k_lds, kb * 32, lane, qf);
         }
         // online softmax in the scaled log2 domain: p = 2^(s*c2 - m).  Only the ragged last tile pays for
         // key masking; the elementwise work is written on float pairs (v_pk_fma_f32 / v_pk_add_f32).
@@ -302,12 +299,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
                     if (kt * 64 + kb * 32 + frag_row(r, lane) >= N) s[kb][r] = NEG_BIG;
         }
         float mx = NEG_BIG;
-        if (!(MAEST_ABLATE_FWD & 1)) {
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-        }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float m_new = fmaxf(m_run, mx * c2);
         const float alpha = fast_exp2<T>(m_run - m_new);
@@ -320,7 +315,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
             for (int r = 0; r < 16; r += 2) {
                 const f32x2_t sv = {s[kb][r], s[kb][r + 1]};
                 const f32x2_t e = __builtin_elementwise_fma(sv, c2v, nm);
-                const f32x2_t pv = (MAEST_ABLATE_FWD & 1) ? sv : f32x2_t{fast_exp2<T>(e[0]), fast_exp2<T>(e[1])};
+                const f32x2_t pv = {fast_exp2<T>(e[0]), fast_exp2<T>(e[1])};
                 s[kb][r] = pv[0];
                 s[kb][r + 1] = pv[1];
                 ps += pv;
@@ -332,13 +327,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
             for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
         // O^T[d][q] += V^T[d][key] P^T[key][q]   (V^T gathered from the row-major V tile)
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            if (!(MAEST_ABLATE_FWD & 2)) mma_transposed<T, X3>(o, v_lds, kb * 32, lane, s[kb]);
-            else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) o[kb][r] += s[kb][r];
-            }
-        }
+        for (int kb = 0; kb < 2; ++kb) mma_transposed<T, X3>(o, v_lds, kb * 32, lane, s[kb]);
         }
         if (more) {
             char* nk = smem + ((kt + 1) & 1) * 2 * C::TILE;
@@ -352,7 +341,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
     if (wave_active) {      // (wave-uniform)
         // (staging O through LDS for whole-row stores was measured: no gain at N = 290, -16 % at N = 560;
         // profiles/r03_attn_fwd_ablation.txt.  The 16-byte pieces of store_dT_ok need no LDS and no barrier.)
-        const bool ok = q < N && (!(MAEST_ABLATE_FWD & 16) || l_tot == 12345.0f);
+        const bool ok = q < N;
         if (sizeof(T) == 4 && out_a3) {
             store_dT_split3(o, reinterpret_cast<bf16_t*>(out) + ((int64_t)b * N + (ok ? q : 0)) * (3 * OUT_LD) + head * HD, lane, inv, ok);
         } else {
@@ -667,9 +656,7 @@ __device__ __forceinline__ void mma_transposed_swz(f32x16_t (&acc)[2], const cha
 // register-staged form (profiles/r03_attn_fwd_ablation.txt) prices its K / V refills at a quarter of the kernel and its
 // LDS bank-conflict cycles at 23 % (padded pitch: the transpose reads cost twice their ideal cycles).  Rows beyond N repeat row
 // N - 1 (the DMA clamps): their scores are masked on the last tile as before, so P = 0 meets a finite V row.
-#ifndef MAEST_FWD_RING
-#define MAEST_FWD_RING 2      // ring depth of the K / V tiles: 2 = one tile ahead (32 KiB, 4 workgroups per CU); 3 = two ahead (48 KiB, 3 per CU)
-#endif
+constexpr int RING = 2;       // ring depth of the K / V tiles: one tile ahead (32 KiB, 4 workgroups per CU)
 // NW = waves per workgroup = 32-query blocks per workgroup (round 3, last part).  Every workgroup of a (batch, head) streams
 // ALL of its K / V tiles from L2 into its own LDS, so fewer, larger workgroups move fewer bytes (N = 560: 3 x 192 or 3 x 256
 // rows instead of 5 x 128).  Measured (scratch/attn_fwd_waves.py, profiles/r03_attn_fwd_waves.txt; bit-equal at every NW):
@@ -679,9 +666,7 @@ __device__ __forceinline__ void mma_transposed_swz(f32x16_t (&acc)[2], const cha
 // workgroups already hide, not bandwidth.  Only N <= 256 with more than 128 rows gains (N = 129: 56 against 65 us).
 // attn_fwd_waves() therefore keeps NW = 4; MAEST_OPT_ATTN_FWD_WAVES forces another for tests and A/B.
 template <int NW>
-struct FwdWgs { static constexpr int value = MAEST_FWD_RING == 3 ? (NW <= 5 ? 3 : 2) : (16 / NW); };
-template <int NW>
-__global__ __launch_bounds__(NW * 64, FwdWgs<NW>::value) void attn_fwd_dma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+__global__ __launch_bounds__(NW * 64, 16 / NW) void attn_fwd_dma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                               float* __restrict__ lse, int B, int N, float sc_c2, int q_rows) {
     using T = bf16_t;
     using C = AttnCfg<T>;
@@ -702,8 +687,6 @@ __global__ __launch_bounds__(NW * 64, FwdWgs<NW>::value) void attn_fwd_dma_kerne
     const T* vbase = qbase + 2 * NHEADS * HD;
 
     const int ntiles = (N + 63) / 64;
-    constexpr int RING = MAEST_FWD_RING;      // 2: one tile ahead (32 KiB, 4 workgroups per CU); 3: two ahead (48 KiB, 3 per CU)
-    static_assert(RING == 2 || NW == 4, "the counted waits of the three-deep ring assume four pieces per wave and tile");
     // this wave's share of the 16 one-KiB pieces (8 of K, 8 of V) of key tile kt -> ring buffer kt % RING.  Pieces 2w, 2w + 1 of
     // K and of V at NW = 4; dealt round-robin otherwise (the waits below are vmcnt(0): the count per wave does not matter)
     auto tile_dma = [&](int kt) {
@@ -721,7 +704,6 @@ __global__ __launch_bounds__(NW * 64, FwdWgs<NW>::value) void attn_fwd_dma_kerne
         }
     };
     tile_dma(0);
-    if (RING == 3 && ntiles > 1) tile_dma(1);
     chunk16 qf[C::STEPS];
     row_frags_load<T>(qf, qbase, QKV_LD, q, N, h);
 
@@ -732,8 +714,7 @@ __global__ __launch_bounds__(NW * 64, FwdWgs<NW>::value) void attn_fwd_dma_kerne
         for (int r = 0; r < 16; ++r) o[db][r] = 0.0f;
     float m_run = NEG_BIG, l_run = 0.0f;
     const float c2 = sc_c2;
-    if (RING == 3 && ntiles > 1) __builtin_amdgcn_s_waitcnt(0x0F74);      // vmcnt(4): tile 0 and the Q fragments landed, tile 1 may fly
-    else MAEST_ATTN_WAIT_VM0();
+    MAEST_ATTN_WAIT_VM0();
     __builtin_amdgcn_s_barrier();
     for (int kt = 0; kt < ntiles; ++kt) {
         const char* k_lds = smem + (kt % RING) * 2 * TILE128;
@@ -786,8 +767,7 @@ __global__ __launch_bounds__(NW * 64, FwdWgs<NW>::value) void attn_fwd_dma_kerne
             for (int kb = 0; kb < 2; ++kb) mma_transposed_swz(o, v_lds, kb * 32, lane, s[kb]);   // O^T[d][q] += V^T[d][key] P^T[key][q]
         }
         // this wave's share of the next tile has landed; behind the barrier everybody's has, and nobody reads this tile any more
-        if (RING == 3 && issued) __builtin_amdgcn_s_waitcnt(0x0074);      // vmcnt(4) lgkmcnt(0): only the newest tile may fly
-        else __builtin_amdgcn_s_waitcnt(0x0070);        // vmcnt(0) lgkmcnt(0)
+        __builtin_amdgcn_s_waitcnt(0x0070);        // vmcnt(0) lgkmcnt(0)
         __builtin_amdgcn_s_barrier();
     }
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -1187,24 +1167,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_dma_kernel(const bf16_t* _
     store_dT_ok<T>(dq, dqkv + ((int64_t)b * N + (q_ok ? q : 0)) * QKV_LD + head * HD, lane, sc_dq, q_ok);
 }
 
-// MAEST_ATTN_PROF: timing instrumentation only (scratch/attn_prof.py builds a second library with it; never defined in
-// the product build): shader-clock stamps of every wave of the workgroups with blockIdx % 256 == 5, per query tile.
-#ifdef MAEST_ATTN_PROF
-__device__ unsigned long long* g_attn_prof = nullptr;
-#define PROF_DECL() unsigned long long pst[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define PROF_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); pst[k] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define PROF_FLUSH(t) do { if (g_attn_prof != nullptr && (blockIdx.x & 255) == 5 && lane == 0) { \
-        unsigned long long* d_ = g_attn_prof + ((((blockIdx.x >> 8) * FB_MAXW + wave) * 16 + (t)) * 8); \
-        for (int k_ = 0; k_ < 8; ++k_) d_[k_] = pst[k_]; } } while (0)
-#define PROF_FLUSH3(g) do { if (g_attn_prof != nullptr && blockIdx.x == 5 && lane == 0 && (g) < 128) { \
-        unsigned long long* d_ = g_attn_prof + ((wave * 128 + (g)) * 8); \
-        for (int k_ = 0; k_ < 8; ++k_) d_[k_] = pst[k_]; } } while (0)
-#else
-#define PROF_DECL() ((void)0)
-#define PROF_STAMP(k) ((void)0)
-#define PROF_FLUSH(t) ((void)0)
-#define PROF_FLUSH3(g) ((void)0)
-#endif
 __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf16_t* __restrict__ qkv,
                                                                         const bf16_t* __restrict__ dout,
                                                                         const float* __restrict__ lse,
@@ -1239,9 +1201,6 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
 
     const bool key_wave = wave < nkw;
     const int aux = wave - nkw;                    // 0: Q feeder + dQ[:, 0:32], 1: dO feeder + dQ[:, 32:64]; >= 2: filler
-#ifdef MAEST_ATTN_PROF
-    const unsigned long long prof_t0 = __builtin_amdgcn_s_memtime();
-#endif
 
     // ---- prologue, all waves: K of every key block -> LDS by DMA
     dma_rows128(k_lds, kbase, QKV_LD, 0, wave, nkw * 4, nwaves, N, lane);
@@ -1262,9 +1221,7 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
         MAEST_ATTN_WAIT_VM0();                             // this wave's share of the K DMA (and its fragments) landed
         __builtin_amdgcn_s_barrier();                      // K in LDS, query tile 0 staged
         int buf = 0;
-        PROF_DECL();
         for (int t = 0; t < nqt; ++t) {
-            PROF_STAMP(0);
             const char* q_lds = qbuf0 + buf * F2_QBUF;
             const char* do_lds = q_lds + 32 * 128;
             const float* lse_lds = reinterpret_cast<const float*>(q_lds + 2 * 32 * 128);
@@ -1274,7 +1231,6 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
             for (int r = 0; r < 16; ++r) { s[r] = 0.0f; dp[r] = 0.0f; }
             mma_rows_swz(s, q_lds, 0, lane, kf);         // S[q][key]
             mma_rows_swz(dp, do_lds, 0, lane, vf);       // dP[q][key]
-            PROF_STAMP(1);
             char* ds_row = ds0 + (t & 1) * DSBUF + key * FB_DS_PITCH;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -1297,16 +1253,11 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
                 w[1] = key_ok ? pack_bf2(dp[4 * g + 2], dp[4 * g + 3]) : 0u;
                 *reinterpret_cast<chunk8*>(ds_row + ql * 2) = w;
             }
-            PROF_STAMP(2);
             mma_transposed_swz(dv, do_lds, 0, lane, s);   // dV^T[d][key] += dO^T[d][q] P[q][key]
             mma_transposed_swz(dk, q_lds, 0, lane, dp);   // dK^T[d][key] += Q^T[d][q] dS[q][key]
-            PROF_STAMP(3);
             buf = buf == 2 ? 0 : buf + 1;
             __builtin_amdgcn_s_waitcnt(0xC07F);           // lgkmcnt(0): the dS tile is written
-            PROF_STAMP(4);
             __builtin_amdgcn_s_barrier();
-            PROF_STAMP(5);
-            PROF_FLUSH(t);
         }
         __builtin_amdgcn_s_barrier();                      // the aux waves are done with K and the last dS tile
         // dK / dV: registers -> this wave's private LDS patch (row = key, 128 B of d) -> whole rows, 16 B per lane
@@ -1362,8 +1313,8 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
         // K^T[32 d of this wave][every key] stays in REGISTERS for the whole (batch, head) (80 registers at 10 key blocks: the
         // aux waves have them to spare under the 168 budget), gathered once from the K tile after the first barrier; a dQ
         // job then reads only its dS^T fragments -- two blocks ahead of the MFMAs that consume them.  (The per-tile
-        // timeline, scratch/attn_prof.py, showed the aux waves arriving LAST at every barrier: 2200 of their 3650 cycles
-        // per tile were this product, 16 transpose reads in front of every 4 MFMAs.)
+        // timeline, profiles/r03_attn_bwd_timeline_fused2.txt, showed the aux waves arriving LAST at every barrier:
+        // 2200 of their 3650 cycles per tile were this product, 16 transpose reads in front of every 4 MFMAs.)
         chunk16 ktf[FB_MAXW - 2][2];
         auto kt_load = [&]() {
             if (aux > 1) return;
@@ -1414,26 +1365,18 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_s_barrier();                      // K in LDS, query tile 0 staged (tile 1 landed too)
         kt_load();
-        PROF_DECL();
         for (int t = 0; t < nqt; ++t) {
             // Everything issued one step ago has landed by now: the DMA of tile t + 1, and the dQ stores of job
             // t - 2, which were issued BEFORE the dQ product of that step -- a store issued right in front of this
             // wait would put its latency on the critical path (vmcnt counts stores too on gfx950).
-            PROF_STAMP(0);
             MAEST_ATTN_WAIT_VM0();
-            PROF_STAMP(1);
             stat_store(st_next, t + 1);
             tile_dma(t + 2);                               // lands during this step and the next one
             st_next = stat_load(t + 2);
             dq_store(dq_prev, t - 2);
-            PROF_STAMP(2);
             if (t > 0) dq_compute(dq_prev, t - 1);
-            PROF_STAMP(3);
             __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): statistics of tile t + 1 are in LDS
-            PROF_STAMP(4);
             __builtin_amdgcn_s_barrier();
-            PROF_STAMP(5);
-            PROF_FLUSH(t);
         }
         dq_store(dq_prev, nqt - 2);
         dq_compute(dq_prev, nqt - 1);
@@ -1448,12 +1391,6 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused2_kernel(const bf1
         __builtin_amdgcn_s_barrier();                      // LDS may be reused by the key waves' epilogue
         __syncthreads();
     }
-#ifdef MAEST_ATTN_PROF
-    {
-        unsigned long long pst[8] = {prof_t0, __builtin_amdgcn_s_memtime(), __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0, 0};
-        PROF_FLUSH(15);
-    }
-#endif
 }
 
 static int attn_bwd_fused2_smem(int N) {
@@ -1462,7 +1399,7 @@ static int attn_bwd_fused2_smem(int N) {
 }
 
 // =================================================================================== fused backward, persistent (bf16, 257 <= N <= 320)
-// The per-tile timeline of attn_bwd_fused2_kernel (MAEST_ATTN_PROF, scratch/attn_prof.py; B = 256, N = 290) shows a workgroup
+// The per-tile timeline of attn_bwd_fused2_kernel (profiles/r03_attn_bwd_timeline_fused2.txt; B = 256, N = 290) shows a workgroup
 // living 58 k cycles of which 12.4 k pass before its first query tile (K, the K / V fragments and two query tiles fetched
 // by all 256 workgroups of a round at once: 150 KB per CU at the ~11 B/clk/CU an all-CU burst gets) and 7 k after its last
 // one (dK / dV staging and stores): a third of the time the matrix pipe has nothing to do, and HBM idles during the tiles.
@@ -1542,9 +1479,7 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
         __builtin_amdgcn_s_barrier();
         int it = it0, t = 0, slot = 0;                     // the tile of this step
         int it2 = it0, t2 = 2, slot2 = 2;                  // the tile two steps ahead (its DMA is issued now)
-        PROF_DECL();
         for (int g = 0; g < total; ++g) {
-            PROF_STAMP(0);
             const bool first = t == 0, last = t == nqt - 1;
             const int itn = it + stride;                   // next item of this workgroup
             // the lane index as the DMA address arithmetic sees it is redefined every step: hoisted out of the loop, the
@@ -1554,17 +1489,14 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
 #if defined(__AMDGCN__)
             asm volatile("" : "+v"(lv));
 #endif
-#ifndef MAEST_ABLATE_F3
-#define MAEST_ABLATE_F3 0      // timing experiments only (scratch/attn_ablate.sh; results wrong on purpose): bit 0 no dK / dV stores,
-#endif                         // 1 no K / V prefetch, 2 no tile pieces, 3 no dQ product, 4 no dQ stores, 5 no softmax math, 6 no dV / dK products
-            if (first && g > 0 && !(MAEST_ABLATE_F3 & 1)) {  // dK, dV of the item that ended a step ago
+            if (first && g > 0) {                             // dK, dV of the item that ended a step ago
                 T* row = dq_of(it - stride) + (uint32_t)(key * QKV_LD + NHEADS * HD);
                 store_dT_rows16(dk, row, lane, sc_dk, key_ok);
                 store_dT_rows16(dv, row + NHEADS * HD, lane, 1.0f, key_ok);
             }
             // LDS-DMA of this step: the next item's K / V piece first, the tile piece second
             bool pref = false;
-            if (!first && itn < items && !(MAEST_ABLATE_F3 & 2)) {
+            if (!first && itn < items) {
                 const int pidx = (t - 1) * nkw + wave;
                 if (pidx < 8 * nkw) {
                     const bool isv = pidx >= 4 * nkw;
@@ -1574,7 +1506,7 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
                     pref = true;
                 }
             }
-            const bool tp = wave < 8 && g + 2 < total && !(MAEST_ABLATE_F3 & 4);
+            const bool tp = wave < 8 && g + 2 < total;
             if (tp) tile_piece(it2, t2, slot2, lv);
             if (first) {
                 row_frags_lds_swz(kf, k_lds, key, h);
@@ -1591,10 +1523,8 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
             f32x16_t s, dp;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { s[r] = 0.0f; dp[r] = 0.0f; }
-            PROF_STAMP(1);
             mma_rows_swz(s, q_lds, 0, lane, kf);         // S[q][key]
             mma_rows_swz(dp, do_lds, 0, lane, vf);       // dP[q][key]
-            PROF_STAMP(2);
             char* ds_row = ds0 + (g & 1) * DSBUF + key * FB_DS_PITCH;
 #pragma unroll
             for (int gq = 0; gq < 4; ++gq) {
@@ -1607,8 +1537,8 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
                     const f32x2_t sv = {s[r], s[r + 1]}, nl = {-l4[e], -l4[e + 1]};
                     const f32x2_t dpv = {dp[r], dp[r + 1]}, dl = {d4[e], d4[e + 1]};
                     const f32x2_t ev = __builtin_elementwise_fma(sv, c2v, nl);
-                    const f32x2_t pv = (MAEST_ABLATE_F3 & 32) ? ev : f32x2_t{fast_exp2<T>(ev[0]), fast_exp2<T>(ev[1])};
-                    const f32x2_t dsv = (MAEST_ABLATE_F3 & 32) ? dpv : pv * (dpv - dl);
+                    const f32x2_t pv = {fast_exp2<T>(ev[0]), fast_exp2<T>(ev[1])};
+                    const f32x2_t dsv = pv * (dpv - dl);
                     s[r] = pv[0]; s[r + 1] = pv[1];       // P
                     dp[r] = dsv[0]; dp[r + 1] = dsv[1];   // dS (unscaled)
                 }
@@ -1617,25 +1547,15 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
                 w[1] = key_ok ? pack_bf2(dp[4 * gq + 2], dp[4 * gq + 3]) : 0u;
                 *reinterpret_cast<chunk8*>(ds_row + ql * 2) = w;
             }
-            PROF_STAMP(3);
-            if (!(MAEST_ABLATE_F3 & 64)) {
             mma_transposed_swz(dv, do_lds, 0, lane, s);   // dV^T[d][key] += dO^T[d][q] P[q][key]
             mma_transposed_swz(dk, q_lds, 0, lane, dp);   // dK^T[d][key] += Q^T[d][q] dS[q][key]
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { dv[0][r] += s[r]; dk[0][r] += dp[r]; }
-            }
-            PROF_STAMP(4);
             // end of step: the pieces issued a step ago have landed (only this step's may still fly); at an item's last
             // step its K / V prefetch piece too (the next step reads K and V)
             const int keep = (tp ? 1 : 0) + ((pref && !last) ? 1 : 0);
             if (keep == 0) __builtin_amdgcn_s_waitcnt(0x0070);          // vmcnt(0) lgkmcnt(0)
             else if (keep == 1) __builtin_amdgcn_s_waitcnt(0x0071);     // vmcnt(1) lgkmcnt(0)
             else __builtin_amdgcn_s_waitcnt(0x0072);                    // vmcnt(2) lgkmcnt(0)
-            PROF_STAMP(5);
             __builtin_amdgcn_s_barrier();
-            PROF_STAMP(6);
-            PROF_FLUSH3(g);
             slot = slot == 2 ? 0 : slot + 1;
             slot2 = slot2 == 2 ? 0 : slot2 + 1;
             if (++t == nqt) { t = 0; it = itn; }
@@ -1648,10 +1568,6 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
         }
     } else {
         // =============================================================================== aux waves
-#ifndef MAEST_F3_AUX_PRIO
-#define MAEST_F3_AUX_PRIO 0
-#endif
-        if (MAEST_F3_AUX_PRIO > 0) __builtin_amdgcn_s_setprio(MAEST_F3_AUX_PRIO);   // (the youngest waves of the workgroup lose every arbitration)
         const float* sbase = aux == 0 ? lse : delta;       // per-row statistic this wave carries: lse (scaled) / delta
         auto stat_load = [&](int it, int t) -> float {     // (unconditional, clamped)
             int row = t * 32 + (lane & 31);
@@ -1714,25 +1630,16 @@ __global__ __launch_bounds__(FB_MAXW * 64) void attn_bwd_fused3_kernel(const bf1
         int it2 = it0, t2 = 2;                             // two ahead (its statistic is loaded now)
         T* out1 = nullptr; int tj1 = 0;                    // job g - 1: computed now
         T* out2 = nullptr; int tj2 = 0;                    // job g - 2: stored now
-        PROF_DECL();
         for (int g = 0; g < total; ++g) {
             // everything issued a step ago has landed: the statistic of tile g + 1 and the dQ stores of job g - 3
-            PROF_STAMP(0);
             MAEST_ATTN_WAIT_VM0();
-            PROF_STAMP(1);
             if (g + 1 < total) stat_store(st_next, t1, slot1);
             if (g + 2 < total) st_next = stat_load(it2, t2);
-            if (out2 != nullptr && !(MAEST_ABLATE_F3 & 16)) dq_store(dq_prev, out2, tj2);
-            PROF_STAMP(2);
-            if (out1 != nullptr && !(MAEST_ABLATE_F3 & 8)) dq_compute(dq_prev, g - 1);
-            PROF_STAMP(3);
+            if (out2 != nullptr) dq_store(dq_prev, out2, tj2);
+            if (out1 != nullptr) dq_compute(dq_prev, g - 1);
             if (t == 0 && g > 0) kt_load();                // the item that starts now (its K arrived during the previous one)
-            PROF_STAMP(4);
             __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0): statistics of tile g + 1 are in LDS
-            PROF_STAMP(5);
             __builtin_amdgcn_s_barrier();
-            PROF_STAMP(6);
-            PROF_FLUSH3(g);
             out2 = out1; tj2 = tj1;
             out1 = dq_of(it); tj1 = t;
             slot1 = slot1 == 2 ? 0 : slot1 + 1;
@@ -1773,7 +1680,7 @@ static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N,
         if (afw == 0 || afw == 2 || afw == 3) {     // K / V tiles by LDS-DMA (unpadded, swizzled); 2 forces this form at any N
             const int nw = attn_fwd_waves(N, q_rows);
             const dim3 g(((N + nw * 32 - 1) / (nw * 32)) * NHEADS * B);
-            const int lds = MAEST_FWD_RING * 2 * 64 * 128;
+            const int lds = RING * 2 * 64 * 128;
 #define MAEST_FWD_LAUNCH(NW_) hipLaunchKernelGGL(attn_fwd_dma_kernel<NW_>, g, dim3(NW_ * 64), lds, st, (const bf16_t*)qkv, \
                                                  (bf16_t*)out, lse, B, N, sc.c2, q_rows)
             if (nw == 5) MAEST_FWD_LAUNCH(5);
@@ -1878,11 +1785,6 @@ static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, c
 
 using namespace maest;
 
-#ifdef MAEST_ATTN_PROF
-extern "C" int maest_debug_attn_prof(void* p) {
-    return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_attn_prof), &p, sizeof(p));
-}
-#endif
 
 extern "C" int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B, int N, int dtype, float scale,
                                    int q_rows, void* stream) {

@@ -65,24 +65,6 @@ constexpr int PW_Q0 = 2 * PW_RING * PW_TILE;  // swizzled like a K tile): 72 KiB
 constexpr int PW_LDS = PW_Q0 + PW_ROWS * 128;
 constexpr float PW_HOT = 4096.0f;             // a tile's (half-)row sum above this sends the wave to the rescale path
 constexpr float PW_COLD = 1.0e-30f;           // ... and, on an item's first tile (scores taken against m = 0), one below this
-#ifndef PW_SUM
-#define PW_SUM 0          // row sums: 0 = two v_add_f32 per slice, 1 = one v_dot2c_f32_bf16 on the packed word (timing variants)
-#endif
-#ifndef PW_CHAIN
-#define PW_CHAIN 0        // MFMA order inside a group: 0 = the two accumulators alternate, 1 = one accumulator's four MFMAs back to back
-#endif
-#ifndef PW_DMAPOS
-#define PW_DMAPOS 0       // where a tile's eight LDS-DMA requests ride (timing variants)
-#endif
-#ifndef PW_ORDER
-#define PW_ORDER 0        // MFMAs of a pipeline region: 0 = the eight P V products, then the eight S' products; 1 = alternating (P V in the even
-#endif                    // slots, S' in the odd ones: four MFMAs between two on the same accumulator): equal time (r05_attn_fwd_pw_variants.txt)
-#ifndef PW_TAILNOP
-#define PW_TAILNOP 0      // 1: the 12 wait states behind a unit's last S' MFMA also inside the pipeline regions (timing variant; see pw_s_mfma)
-#endif
-#ifndef PW_ABLATE
-#define PW_ABLATE 0       // timing experiments only (scratch/pw_ablate.sh; results wrong on purpose): bit 0 no LDS-DMA requests, 1 no
-#endif                    // barrier / vmcnt wait, 2 no softmax slices, 3 no MFMAs, 4 no fragment reads, 5 no stores, 6 no Q take, 8 v_mov for v_exp
 
 // register map (device build)
 constexpr int PW_A_O = 0;                     // O^T[i][db]       16 registers each: a0   .. a95
@@ -107,11 +89,6 @@ struct PwCtx {
     uint32_t kaddr[4];           // LDS byte addresses (ring slot included) of this lane's K row chunks
     uint32_t vaddr[2][2];        // ... of its transpose-read pieces: [d block][row / row + 8]
     int kslot, vslot;            // ring slot those addresses point into (wave-uniform)
-#ifdef PW_PROF
-    unsigned long long* pp;      // (timing build: stamp buffer in LDS, next index, this workgroup is the profiled one, lane)
-    int pidx, plane;
-    bool pon;
-#endif
 #if !PW_DEV
     f32x16_t o[PW_QB][2];        // (host emulator: the state the device keeps in owned registers)
     chunk16 qf[PW_QB][4];
@@ -125,29 +102,12 @@ struct PwCtx {
 #endif
 };
 
-// PW_PROF: timing instrumentation only (scratch/pw_prof.py builds a second library with it; never defined in the product
-// build): shader-clock stamps of both waves of workgroup 5, one per pipeline region / barrier / item phase, parked in LDS behind
-// the kernel's own 72 KiB (no vector-memory operation: the counted vmcnt waits stay exact) and copied out at the end.
-#ifdef PW_PROF
-__device__ unsigned long long* g_pw_prof = nullptr;
-#define PW_STAMP() do { if (c.pon && c.pidx < 512) { if (c.plane == 0) c.pp[c.pidx] = __builtin_amdgcn_s_memtime(); ++c.pidx; } } while (0)
-#ifdef PW_PROF_SLOTS
-#define PW_STAMP_SLOT() PW_STAMP()
-#else
-#define PW_STAMP_SLOT() ((void)0)
-#endif
-#else
-#define PW_STAMP() ((void)0)
-#define PW_STAMP_SLOT() ((void)0)
-#endif
-
 // One LDS-DMA piece (1 KiB): lane l's 16 bytes come from (char*)sbase + voff + IMM (sbase wave-uniform, in SGPRs) and land at
 // smem + dst + 16 l.  Inline asm for the reasons given at dma16 (attn_common.h); the waits are placed by hand.  M0 is left
 // holding the LDS address: nothing else in this kernel uses it (no indirect register indexing, no builtin LDS-DMA).
 template <int IMM>
 __device__ __forceinline__ void pw_dma(const bf16_t* sbase, uint32_t voff, char* smem, uint32_t dst) {
 #if PW_DEV
-    if (PW_ABLATE & 1) return;
     // (the instruction's immediate offset is added to the LDS address as well as to the global one: take it out again)
     const uint32_t lds = __builtin_amdgcn_readfirstlane(dst - IMM + (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem);
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3"
@@ -162,13 +122,11 @@ __device__ __forceinline__ void pw_dma(const bf16_t* sbase, uint32_t voff, char*
 // previous barrier whatever the stores in between do: fewer than 8 left in flight means at most the newest tile's pieces.
 __device__ __forceinline__ void pw_wait_all() {          // everything: kernel start
 #if PW_DEV
-    if (PW_ABLATE & 2) return;
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : : : "memory");
 #endif
 }
 __device__ __forceinline__ void pw_wait_tile() {         // in front of a tile's barrier: pieces up to the previous barrier's, LDS reads
 #if PW_DEV
-    if (PW_ABLATE & 2) return;
     asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" : : : "memory");
 #endif
 }
@@ -184,7 +142,6 @@ __device__ __forceinline__ void pw_wait_lds() {      // every LDS read this wave
 }
 __device__ __forceinline__ void pw_barrier() {
 #if PW_DEV
-    if (PW_ABLATE & 2) return;
     asm volatile("s_barrier" : : : "memory");
 #else
     __syncthreads();
@@ -309,7 +266,6 @@ __device__ __forceinline__ void pw_k_read(PwCtx& c) {
     constexpr int KB = K & 1, J = K >> 1;
 #if PW_DEV
     constexpr int A = (SET ? PW_A_K2 : PW_A_K) + (4 * KB + J) * 4;
-    if (!(PW_ABLATE & 16))
     asm volatile("ds_read_b128 a[%c1:%c2], %0 offset:%c3" : : "v"(c.kaddr[J]), "i"(A), "i"(A + 3), "i"(KB * 4096));
 #else
     c.kf[SET][KB][J] = *reinterpret_cast<const chunk16*>(c.lds + c.kaddr[J] + KB * 4096);
@@ -326,7 +282,6 @@ __device__ __forceinline__ void pw_v_read(PwCtx& c) {
     constexpr int KB = K >> 2, S2 = (K >> 1) & 1, DB = K & 1;
 #if PW_DEV
     constexpr int A = PW_A_V + ((2 * KB + DB) * 2 + S2) * 4;
-    if (!(PW_ABLATE & 16))
     asm volatile("ds_read_b64_tr_b16 a[%c2:%c3], %0 offset:%c6\n\tds_read_b64_tr_b16 a[%c4:%c5], %1 offset:%c6"
                  : : "v"(c.vaddr[DB][0]), "v"(c.vaddr[DB][1]), "i"(A), "i"(A + 1), "i"(A + 2), "i"(A + 3), "i"(KB * 4096 + S2 * 2048));
 #else
@@ -364,9 +319,8 @@ __device__ __forceinline__ void pw_read_v(PwCtx& c) { pw_read_v_all(c, std::make
 // (-2.5 % on the kernel: profiles/r05_attn_fwd_pw_variants.txt)
 template <int I, int BUF, int SET, int K, bool TILE0, bool NOPS = true>
 __device__ __forceinline__ void pw_s_mfma(PwCtx& c) {
-    constexpr int KB = PW_CHAIN ? K >> 2 : K & 1, J = PW_CHAIN ? K & 3 : K >> 1;
+    constexpr int KB = K & 1, J = K >> 1;
 #if PW_DEV
-    if (PW_ABLATE & 8) return;
     constexpr int KF = (SET ? PW_A_K2 : PW_A_K) + (4 * KB + J) * 4, Q = PW_A_Q + (4 * I + J) * 4, S = PW_V_S + (2 * BUF + KB) * 16, NM = PW_V_NM + 16 * I;
     if constexpr (J == 0 && TILE0) {
         if constexpr (K == 0)
@@ -380,7 +334,7 @@ __device__ __forceinline__ void pw_s_mfma(PwCtx& c) {
         else
             asm volatile("v_mfma_f32_32x32x16_" MAEST_T16 " v[%c0:%c1], a[%c2:%c3], a[%c4:%c5], v[%c6:%c7]"
                          : : "i"(S), "i"(S + 15), "i"(KF), "i"(KF + 3), "i"(Q), "i"(Q + 3), "i"(NM), "i"(NM + 15));
-    } else if constexpr (K == 7 && (NOPS || PW_TAILNOP)) {
+    } else if constexpr (K == 7 && NOPS) {
         asm volatile("v_mfma_f32_32x32x16_" MAEST_T16 " v[%c0:%c1], a[%c2:%c3], a[%c4:%c5], v[%c0:%c1]\n\ts_nop 7\n\ts_nop 3"
                      : : "i"(S), "i"(S + 15), "i"(KF), "i"(KF + 3), "i"(Q), "i"(Q + 3));
     } else {
@@ -400,10 +354,9 @@ __device__ __forceinline__ void pw_s_mfma(PwCtx& c) {
 // K & 1) into the O registers, B = a chunk of P buffer BUF.  TILE0: the first two take C = 0 (O[I] needs no clearing).
 template <int I, int BUF, int K, bool TILE0>
 __device__ __forceinline__ void pw_pv_mfma(PwCtx& c) {
-    constexpr int KB = PW_CHAIN ? (K >> 1) & 1 : K >> 2, S2 = PW_CHAIN ? K & 1 : (K >> 1) & 1, DB = PW_CHAIN ? K >> 2 : K & 1;
+    constexpr int KB = K >> 2, S2 = (K >> 1) & 1, DB = K & 1;
     constexpr bool FIRSTOF = KB == 0 && S2 == 0;       // this accumulator's first MFMA of the group
 #if PW_DEV
-    if (PW_ABLATE & 8) return;
     constexpr int O = PW_A_O + (2 * I + DB) * 16, V = PW_A_V + ((2 * KB + DB) * 2 + S2) * 4, P = PW_V_PK + ((2 * BUF + KB) * 2 + S2) * 4;
     if constexpr (TILE0 && FIRSTOF && K == 0)
         asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_" MAEST_T16 " a[%c0:%c1], a[%c2:%c3], v[%c4:%c5], 0" : : "i"(O), "i"(O + 15), "i"(V), "i"(V + 3), "i"(P), "i"(P + 3));
@@ -439,12 +392,9 @@ __device__ __forceinline__ void pw_pv_products(PwCtx& c) { pw_pv_all<I, BUF, TIL
 // this lane's half already taken out) are padding: their S' becomes -1e30 first.  gfx950: a VALU reading a v_exp result needs one
 // wait state in between (hipcc pads this itself): the callers always put other instructions between the two halves of a slice.
 // Device: exponentials and row sums live in owned registers (PW_V_T ..); pw_sum_begin / pw_sum_end bracket a unit.
-// The row sum is taken over the ROUNDED probabilities -- the values the P V product sees -- by v_dot2c_f32_bf16 against a pair of
-// ones: one instruction per slice instead of two adds.
 __device__ __forceinline__ void pw_sum_begin(PwCtx& c) {
 #if PW_DEV
-    if constexpr (PW_SUM == 1) asm volatile("v_mov_b32 v%c0, 0\n\tv_mov_b32 v%c1, " MAEST_ONE16X2_STR : : "i"(PW_V_T + 2), "i"(PW_V_T + 3));
-    else asm volatile("v_mov_b32 v%c0, 0\n\tv_mov_b32 v%c1, 0" : : "i"(PW_V_T + 2), "i"(PW_V_T + 3));
+    asm volatile("v_mov_b32 v%c0, 0\n\tv_mov_b32 v%c1, 0" : : "i"(PW_V_T + 2), "i"(PW_V_T + 3));
 #else
     c.a0 = 0.0f;
 #endif
@@ -452,8 +402,7 @@ __device__ __forceinline__ void pw_sum_begin(PwCtx& c) {
 __device__ __forceinline__ float pw_sum_end(PwCtx& c) {
 #if PW_DEV
     float r;
-    if constexpr (PW_SUM == 1) asm volatile("s_nop 2\n\tv_mov_b32 %0, v%c1" : "=v"(r) : "i"(PW_V_T + 2));     // (a dot result read by another VALU: 3 wait states)
-    else asm volatile("v_add_f32 %0, v%c1, v%c2" : "=v"(r) : "i"(PW_V_T + 2), "i"(PW_V_T + 3));
+    asm volatile("v_add_f32 %0, v%c1, v%c2" : "=v"(r) : "i"(PW_V_T + 2), "i"(PW_V_T + 3));
     return r;
 #else
     return c.a0;
@@ -463,7 +412,6 @@ template <int BUF, int K, bool MASK, bool SUB>
 __device__ __forceinline__ void pw_sm_exp(PwCtx& c, int klim, float d) {
     constexpr int KB = K >> 3, R = 2 * (K & 7);
 #if PW_DEV
-    if (PW_ABLATE & 4) return;
     constexpr int S = PW_V_S + (2 * BUF + KB) * 16 + R, T0 = PW_V_T + 4 * (K & 1);
     constexpr int KEY0 = KB * 32 + (R & 3) + 8 * (R >> 2), KEY1 = KB * 32 + ((R + 1) & 3) + 8 * ((R + 1) >> 2);
     if constexpr (MASK)
@@ -474,8 +422,7 @@ __device__ __forceinline__ void pw_sm_exp(PwCtx& c, int klim, float d) {
         asm volatile("v_sub_f32 v%c1, v%c3, %0\n\tv_sub_f32 v%c2, v%c4, %0\n\tv_exp_f32 v%c1, v%c1\n\tv_exp_f32 v%c2, v%c2"
                      : : "v"(d), "i"(T0), "i"(T0 + 1), "i"(S), "i"(S + 1));
     else
-        if constexpr ((PW_ABLATE & 256) != 0) asm volatile("v_mov_b32 v%c0, v%c2\n\tv_mov_b32 v%c1, v%c3" : : "i"(T0), "i"(T0 + 1), "i"(S), "i"(S + 1));
-        else asm volatile("v_exp_f32 v%c0, v%c2\n\tv_exp_f32 v%c1, v%c3" : : "i"(T0), "i"(T0 + 1), "i"(S), "i"(S + 1));
+        asm volatile("v_exp_f32 v%c0, v%c2\n\tv_exp_f32 v%c1, v%c3" : : "i"(T0), "i"(T0 + 1), "i"(S), "i"(S + 1));
 #else
     if (MASK) {
         if (KB * 32 + (R & 3) + 8 * (R >> 2) >= klim) c.s[BUF][KB][R] = NEG_BIG;
@@ -489,18 +436,13 @@ template <int BUF, int K>
 __device__ __forceinline__ void pw_sm_fin(PwCtx& c) {
     constexpr int KB = K >> 3, R = 2 * (K & 7);
 #if PW_DEV
-    if (PW_ABLATE & (4 | 512)) return;
     constexpr int P = PW_V_PK + ((2 * BUF + KB) * 2 + (R >> 3)) * 4 + ((R & 7) >> 1), T0 = PW_V_T + 4 * (K & 1), A0 = PW_V_T + 2;
-    if constexpr (PW_SUM == 1)
-        asm volatile("v_cvt_pk_" MAEST_T16 "_f32 v%c4, v%c0, v%c1\n\tv_dot2c_f32_" MAEST_T16 " v%c2, v%c4, v%c3"
-                     : : "i"(T0), "i"(T0 + 1), "i"(A0), "i"(A0 + 1), "i"(P));
-    else
-        asm volatile("v_add_f32 v%c2, v%c2, v%c0\n\tv_add_f32 v%c3, v%c3, v%c1\n\tv_cvt_pk_" MAEST_T16 "_f32 v%c4, v%c0, v%c1"
-                     : : "i"(T0), "i"(T0 + 1), "i"(A0), "i"(A0 + 1), "i"(P));
+    asm volatile("v_add_f32 v%c2, v%c2, v%c0\n\tv_add_f32 v%c3, v%c3, v%c1\n\tv_cvt_pk_" MAEST_T16 "_f32 v%c4, v%c0, v%c1"
+                 : : "i"(T0), "i"(T0 + 1), "i"(A0), "i"(A0 + 1), "i"(P));
 #else
     const uint32_t w = pack_bf2(c.t[K & 1][0], c.t[K & 1][1]);
     c.pk[BUF][KB][R >> 3][(R & 7) >> 1] = w;
-    c.a0 += PW_SUM == 1 ? lo16f(w) + hi16f(w) : c.t[K & 1][0] + c.t[K & 1][1];
+    c.a0 += c.t[K & 1][0] + c.t[K & 1][1];
 #endif
 }
 // a whole unit, outside the pipeline (the rescale path): exp(0) | exp(1) fin(0) | ... | fin(15)
@@ -572,14 +514,7 @@ __device__ __forceinline__ void pw_dma_piece(const PwDma& d, char* smem, int wav
 template <int I, int PAR, bool MASK, bool PV, bool PV0, bool SN, bool SN0, bool KN, int K>
 __device__ __forceinline__ void pw_slot(PwCtx& c, int klim, const PwDma& dm, char* smem, int wave) {
     constexpr int BUF = (PAR + I) & 1;
-    if constexpr (PW_ORDER == 1) {
-        if constexpr ((K & 1) == 0) {
-            if constexpr (PV) pw_pv_mfma<(I + 2) % 3, BUF ^ 1, K / 2, PV0>(c);
-        } else {
-            if constexpr (K == 1 && I == 2 && SN) pw_wait_lds();
-            if constexpr (SN) pw_s_mfma<(I + 1) % 3, BUF ^ 1, (I == 2 ? PAR ^ 1 : PAR), K / 2, SN0, false>(c);
-        }
-    } else if constexpr (K < 8) {
+    if constexpr (K < 8) {
         if constexpr (PV) pw_pv_mfma<(I + 2) % 3, BUF ^ 1, K, PV0>(c);
     } else {
         if constexpr (K == 8 && I == 2 && SN) pw_wait_lds();
@@ -587,18 +522,14 @@ __device__ __forceinline__ void pw_slot(PwCtx& c, int klim, const PwDma& dm, cha
     }
     pw_sm_exp<BUF, K, MASK, false>(c, klim, 0.0f);
     if constexpr (I == 1 && KN && K < 8) pw_k_read<PAR ^ 1, K>(c);          // the next tile's K fragments, into the other set
-    if constexpr (PW_ORDER == 1) {                                         // fragment K / 2 right behind the (previous tile's) product that read it
-        if constexpr (I == 0 && (K & 1)) pw_v_read<K / 2>(c);
-    } else if constexpr (I == 0 && K >= 8 && K < 12) {                     // this tile's V^T fragments, two pieces a slot
+    if constexpr (I == 0 && K >= 8 && K < 12) {                             // this tile's V^T fragments, two pieces a slot
         pw_v_read<2 * (K - 8)>(c);
         pw_v_read<2 * (K - 8) + 1>(c);
     }
-    if constexpr (PW_DMAPOS == 0) {          // region 1: slots 9, 11, 13, 15; region 2: slots 1, 3, 5, 7
-        if constexpr (I == 1 && K >= 8 && (K & 1)) pw_dma_piece<(K - 8) / 4, ((K - 8) / 2) & 1>(dm, smem, wave);
-        if constexpr (I == 2 && K < 8 && (K & 1)) pw_dma_piece<2 + K / 4, (K / 2) & 1>(dm, smem, wave);
-    }
+    // this wave's LDS-DMA requests: region 1: slots 9, 11, 13, 15; region 2: slots 1, 3, 5, 7
+    if constexpr (I == 1 && K >= 8 && (K & 1)) pw_dma_piece<(K - 8) / 4, ((K - 8) / 2) & 1>(dm, smem, wave);
+    if constexpr (I == 2 && K < 8 && (K & 1)) pw_dma_piece<2 + K / 4, (K / 2) & 1>(dm, smem, wave);
     if constexpr (K > 0) pw_sm_fin<BUF, (K > 0 ? K - 1 : 0)>(c);
-    if constexpr (PAR == 1) PW_STAMP_SLOT();
 }
 // T0: the item's first key tile: the scores were taken against m = 0 (C = 0), so the row sum is checked on both sides, and the
 // rescale path SETS the maximum (O[I] and l[I] are still untouched: nothing to bring along).
@@ -639,12 +570,6 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
     if (first >= lim) return;
 
     PwCtx c;
-#ifdef PW_PROF
-    c.pp = reinterpret_cast<unsigned long long*>(smem + PW_LDS) + wave * 512;
-    c.pidx = 0;
-    c.plane = lane;
-    c.pon = blockIdx.x == 5 && g_pw_prof != nullptr;
-#endif
     {
 #if PW_DEV
         const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
@@ -676,7 +601,7 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
         dm.voff_last[e] = (uint32_t)((rc << 12) + (rc << 9)) + col[e & 1];
     }
     auto item_k = [&](int blk) -> const bf16_t* {        // K rows of the item's (batch, head), row 0
-        const int bh = (PW_ABLATE & 128) ? 0 : blk / nrb;      // (bit 7: every item reads the first (batch, head)'s K / V: all L2 hits)
+        const int bh = blk / nrb;
         return qkv + (int64_t)(bh / NHEADS) * N * QKV_LD + NHEADS * HD + (bh % NHEADS) * HD;
     };
     dm.blk = first;
@@ -763,17 +688,13 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
 #define PW_TILE_BODY(PAR, LASTT)                                                                               \
         do {                                                                                                   \
             pw_region<0, PAR, false, LASTT, true, false, true, false>(c, klim_last, dm, smem, wave);           \
-            PW_STAMP();                                                                                        \
             pw_fence();                                                                                        \
             pw_wait_tile();                                                                                     \
             pw_barrier();                                                                                      \
-            PW_STAMP();                                                                                        \
             if (LASTT) q_fetch(next);                                                                          \
             pw_region<1, PAR, false, LASTT, true, false, true, false, !(LASTT)>(c, klim_last, dm, smem, wave); \
-            PW_STAMP();                                                                                        \
             pw_region<2, PAR, false, LASTT, true, false, !(LASTT), false>(c, klim_last, dm, smem, wave);       \
             dma_advance();                                                                                     \
-            PW_STAMP();                                                                                        \
         } while (0)
 
         // item start: m = 0, -m = 0 (tile 0's S' products take the inline constant, later tiles the registers), l = 0
@@ -789,11 +710,9 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
             for (int r = 0; r < 16; ++r) c.negm[i][r] = 0.0f;
 #endif
         }
-        PW_STAMP();
         pw_read_k(c);
         pw_wait_lds();
         pw_s_products<0, 0, true>(c);
-        PW_STAMP();
         if (T == 1) {
             // one key tile: every product of the item is a tile-0 product
             pw_region<0, 0, true, true, false, false, true, true>(c, klim_last, dm, smem, wave);
@@ -810,16 +729,12 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
             // tile 0: its S' products take C = 0, its P V products start O[0], O[1]; O[2]'s start a tile later, on zeros
             pw_o_zero<2>(c);
             pw_region<0, 0, true, false, false, false, true, true>(c, klim_last, dm, smem, wave);
-            PW_STAMP();
             pw_fence();
             pw_wait_tile();
             pw_barrier();
-            PW_STAMP();
             pw_region<1, 0, true, false, true, true, true, true, true>(c, klim_last, dm, smem, wave);
-            PW_STAMP();
             pw_region<2, 0, true, false, true, true, true, false>(c, klim_last, dm, smem, wave);
             dma_advance();
-            PW_STAMP();
             int t = 1;
             for (; t + 1 < T - 1; t += 2) {
                 PW_TILE_BODY(1, false);
@@ -839,12 +754,9 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
 #undef PW_TILE_BODY
 
         // the next item's Q rows (requested a tile ago) before this item's stores join the vector-memory queue
-        PW_STAMP();
         pw_fence();
         pw_wait_q();
-        PW_STAMP();
-        if (!(PW_ABLATE & 64)) { if (q_prescaled) q_take_qs(); else q_take(); }
-        PW_STAMP();
+        if (q_prescaled) q_take_qs(); else q_take();
         // normalise and store this wave's 96 rows (16-byte row pieces), log-sum-exp for the backward
 #if PW_DEV
         asm volatile("s_nop 7\n\ts_nop 7");      // the last MFMAs' results -> v_accvgpr_read
@@ -854,7 +766,7 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
             const int q = rb * PW_ROWS + wave * (32 * PW_QB) + 32 * (I_) + (lane & 31);                        \
             const float l_tot = c.l[I_] + __shfl_xor(c.l[I_], 32, 64);                                         \
             const float inv = 1.0f / l_tot;                                                                    \
-            const bool ok = q < N && !((PW_ABLATE & 32) && l_tot != 12345.0f);                                 \
+            const bool ok = q < N;                                                                             \
             bf16_t* op = out + ((int64_t)b * N + (ok ? q : 0)) * OUT_LD + head * HD;                           \
             store_32d_rows16(pw_o_read<I_, 0>(c), op, lane, inv, ok);                                          \
             store_32d_rows16(pw_o_read<I_, 1>(c), op + 32, lane, inv, ok);                                     \
@@ -865,24 +777,8 @@ __global__ __launch_bounds__(PW_NW * 64, 1) void attn_fwd_pw_kernel(const bf16_t
         PW_STORE(1);
         PW_STORE(2);
 #undef PW_STORE
-        PW_STAMP();
     }
-#ifdef PW_PROF
-    if (g_pw_prof != nullptr && blockIdx.x < 64 && tid == 0) {       // where the dispatcher put this workgroup
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_pw_prof[1024 + blockIdx.x] = xcc;
-    }
-    if (c.pon) {
-        __syncthreads();
-        for (int i = lane; i < 512; i += 64) g_pw_prof[wave * 512 + i] = i < c.pidx ? c.pp[i] : 0ull;
-    }
-#endif
 }
-
-#ifdef PW_PROF
-extern "C" int maest_debug_pw_prof(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_pw_prof), &p, sizeof(p)); }
-#endif
 
 int attn_fwd_pw_launch(const void* qkv, void* out, float* lse, int B, int N, AttnScale sc, bool q_prescaled, hipStream_t st) {
     const int nrb = (N + PW_ROWS - 1) / PW_ROWS;
@@ -890,13 +786,8 @@ int attn_fwd_pw_launch(const void* qkv, void* out, float* lse, int B, int N, Att
     const int per = (total + 7) / 8;
     const int nslots = per < 64 ? per : 64;           // 2 workgroups on each of an XCD's 32 CUs
     static DeviceOnce once;
-#ifdef PW_PROF
-    constexpr int lds_bytes = PW_LDS + 2 * 512 * 8;
-#else
-    constexpr int lds_bytes = PW_LDS;
-#endif
-    ensure_dynamic_lds(once, &attn_fwd_pw_kernel, lds_bytes);
-    hipLaunchKernelGGL(attn_fwd_pw_kernel, dim3(8 * nslots), dim3(PW_NW * 64), lds_bytes, st, (const bf16_t*)qkv, (bf16_t*)out, lse,
+    ensure_dynamic_lds(once, &attn_fwd_pw_kernel, PW_LDS);
+    hipLaunchKernelGGL(attn_fwd_pw_kernel, dim3(8 * nslots), dim3(PW_NW * 64), PW_LDS, st, (const bf16_t*)qkv, (bf16_t*)out, lse,
                        B, N, sc.c2, q_prescaled ? 1 : 0, nrb, total);
     return check_launch("maest_attn_fwd(persistent)");
 }

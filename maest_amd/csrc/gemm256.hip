@@ -343,29 +343,6 @@ __device__ __forceinline__ void epilogueW(char* smem, const f32x16_t (&acc)[2][4
 //     (applied on the DMA source address); a 16-lane ds_read_b128 group then covers all 16 slots of 256 B.
 // ================================================================================================
 
-// MAEST_ABLATE_* : timing experiments only (scratch/probe/ablate_w.sh builds the kernel with parts of the main loop
-// removed; results are wrong on purpose).  Never defined in the product build.
-// MAEST_NT_PRIO (timing experiment; the product build leaves it undefined = 0): wave priority in the main loop of
-// gemm_nt256w_kernel.  0: raised for every COMPUTE phase (the shipped form); 1: never; 2: static -- the second-dispatched
-// half (waves 4-7) at priority 1 for the whole loop, no per-phase flips; 3: COMPUTE phases at priority 3.
-#ifndef MAEST_NT_PRIO
-#define MAEST_NT_PRIO 0
-#endif
-#if MAEST_NT_PRIO == 0
-#define MAEST_NT_PRIO_RAISE() __builtin_amdgcn_s_setprio(1)
-#define MAEST_NT_PRIO_DROP() __builtin_amdgcn_s_setprio(0)
-#elif MAEST_NT_PRIO == 3
-#define MAEST_NT_PRIO_RAISE() __builtin_amdgcn_s_setprio(3)
-#define MAEST_NT_PRIO_DROP() __builtin_amdgcn_s_setprio(0)
-#else
-#define MAEST_NT_PRIO_RAISE() ((void)0)
-#define MAEST_NT_PRIO_DROP() ((void)0)
-#endif
-#ifdef MAEST_ABLATE_NO_BARRIER
-#define MAEST_LOOP_BARRIER() ((void)0)
-#else
-#define MAEST_LOOP_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
 // ---- epilogue of the 128-row variant (MTW = 2: each wave owns 64 x 64 outputs): both wave groups stage their m-tiles at
 // once -- the whole 128 x 256 tile (two passes of 64 rows for the fp32 value + GELU' pair, which would not fit) -- one
 // barrier, then the drain with aux_in prefetched into registers before the staging.
@@ -498,16 +475,7 @@ __global__ __launch_bounds__(512) void gemm_nt256w_kernel(Gemm256Params p) {
     }
 
     chunk16 fa[2][MTW], fb[2][2];
-#ifdef MAEST_ABLATE_NO_DSREAD
-    for (int i = 0; i < 2; ++i) {
-        for (int j = 0; j < MTW; ++j) fa[i][j] = chunk16{MAEST_ONE16X2 + (uint32_t)lane, MAEST_ONE16X2, MAEST_ONE16X2, MAEST_ONE16X2};
-        for (int j = 0; j < 2; ++j) fb[i][j] = chunk16{MAEST_ONE16X2, MAEST_ONE16X2 + (uint32_t)lane, MAEST_ONE16X2, MAEST_ONE16X2};
-    }
-#endif
     auto load_frags = [&](int abuf, int bbuf, int kh) {
-#ifdef MAEST_ABLATE_NO_DSREAD
-        return;
-#endif
         const char* la = smem + abuf * W2_UNIT;
         const char* lb = smem + bbuf * W2_UNIT;
 #pragma unroll
@@ -524,12 +492,9 @@ __global__ __launch_bounds__(512) void gemm_nt256w_kernel(Gemm256Params p) {
     // COMPUTE phase with one operand unit's DMA (this wave's 4 -- or NA -- instructions) spread between the MFMAs: the
     // memory front end accepts about one 8-line instruction per 30 clk per CU, so the four waves of a group
     // feed it at exactly its rate, never in a burst, and a wave is never parked in the queue while it owes MFMAs.
-#ifdef MAEST_ABLATE_ROLLING
-    int roll_q = 0;
-#endif
     auto compute = [&](bool dma, int stage, bool is_b, int buf) {
         const int ndma = is_b ? 4 : NA;
-        MAEST_NT_PRIO_RAISE();
+        __builtin_amdgcn_s_setprio(1);
         if constexpr (X3) {
             // split-bf16: the two k chunks of a fragment pair feed ONE K = 16 MFMA triple (common.h: mma_chunk2)
 #pragma unroll
@@ -552,35 +517,13 @@ __global__ __launch_bounds__(512) void gemm_nt256w_kernel(Gemm256Params p) {
             for (int nt = 0; nt < 2; ++nt) {
 #pragma unroll
                 for (int mt = 0; mt < MTW; ++mt) {
-#ifndef MAEST_ABLATE_NO_MFMA
                     mma_chunk<T>(acc[nt][mt], fb[ks][nt], fa[ks][mt]);
-#endif
                 }
-#ifndef MAEST_ABLATE_NO_DMA
                 const int i = ks * 2 + nt;
                 if (dma && i < ndma) issue_one(stage, is_b, buf, i);
-#endif
             }
         }
-#ifdef MAEST_ABLATE_ROLLING
-        // timing experiment: what would the stores of the PREVIOUS tile's C cost if they rode in this tile's main loop?
-        // One full-line 16-byte store per COMPUTE phase (16 per wave and tile = its 128 x 64 bf16 sub-tile), data from
-        // a fragment register (wrong on purpose), optionally through a wave-private LDS bounce (ROLLING=2).
-        if (roll_q < 16) {
-            const int row = wm * 128 + roll_q * 8 + (lane >> 3);
-            chunk16 v = fa[0][0];
-#if MAEST_ABLATE_ROLLING >= 2
-            char* bounce = smem + 4 * W2_UNIT + wave * 4096 + lane * 16;     // (buffer 4: wrong on purpose)
-            *reinterpret_cast<chunk8*>(bounce) = chunk8{v[0], v[1]};
-            *reinterpret_cast<chunk8*>(bounce + 8) = chunk8{v[2], v[3]};
-            v = *reinterpret_cast<const chunk16*>(bounce + ((lane & 7) ^ 5) * 16 - (lane & 7) * 16);
-#endif
-            __builtin_nontemporal_store(v, reinterpret_cast<chunk16*>(reinterpret_cast<char*>(p.C) +
-                                        ((int64_t)(m0 + row) * p.ldc + n0 + wn * 64) * 2 + (lane & 7) * 16));
-        }
-        ++roll_q;
-#endif
-        MAEST_NT_PRIO_DROP();
+        __builtin_amdgcn_s_setprio(0);
     };
     auto next = [](int b, int by) { b += by; return b >= W2_NBUF ? b - W2_NBUF : b; };
 
@@ -592,9 +535,6 @@ __global__ __launch_bounds__(512) void gemm_nt256w_kernel(Gemm256Params p) {
     issue_unit(2, false, 4);
     MAEST_WAIT_VMCNT(2 * NA + 4);    // stage 0 landed (this wave's share): A_1 B_1 A_2 may still fly
     __builtin_amdgcn_s_barrier();
-#if MAEST_NT_PRIO == 2
-    if (wm == 1) __builtin_amdgcn_s_setprio(1);
-#endif
     if (wm == 1) __builtin_amdgcn_s_barrier();          // stagger (wave-uniform)
     // Per stage j, group A (wm == 0) passes barriers  b1 b2 b3 b4  as
     //   LOAD(j,0) b1 COMPUTE(j,0) b2 LOAD(j,1) b3 COMPUTE(j,1) [vmcnt] b4
@@ -611,28 +551,22 @@ __global__ __launch_bounds__(512) void gemm_nt256w_kernel(Gemm256Params p) {
         const int abuf_prev = next(abuf, W2_NBUF - 2), bbuf_prev = next(bbuf, W2_NBUF - 2);
         load_frags(abuf, bbuf, 0);
         __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0) only
-        MAEST_LOOP_BARRIER();
+        __builtin_amdgcn_s_barrier();
         if (wm == 0) compute(j > 0, j + 1, true, abuf_prev);
         else compute(j > 0, j + 2, false, bbuf_prev);
-        MAEST_LOOP_BARRIER();
+        __builtin_amdgcn_s_barrier();
         load_frags(abuf, bbuf, 1);
         if (wm == 0) {
             __builtin_amdgcn_s_waitcnt(0xC07F);
-            MAEST_LOOP_BARRIER();           // b3
+            __builtin_amdgcn_s_barrier();           // b3
             compute(j > 0, j + 2, false, bbuf_prev);
-#ifndef MAEST_ABLATE_NO_VMWAIT
             MAEST_WAIT_VMCNT(NA);
-#endif
-            MAEST_LOOP_BARRIER();           // b4
+            __builtin_amdgcn_s_barrier();           // b4
         } else {
-#ifndef MAEST_ABLATE_NO_VMWAIT
             __builtin_amdgcn_s_waitcnt(0x0070 | NA);     // vmcnt(NA) lgkmcnt(0)
-#else
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-#endif
-            MAEST_LOOP_BARRIER();           // b4
+            __builtin_amdgcn_s_barrier();           // b4
             compute(true, j + 2, true, abuf);
-            MAEST_LOOP_BARRIER();
+            __builtin_amdgcn_s_barrier();
         }
         abuf = next(abuf, 2);
         bbuf = next(bbuf, 2);
@@ -640,18 +574,6 @@ __global__ __launch_bounds__(512) void gemm_nt256w_kernel(Gemm256Params p) {
     if (wm == 0) __builtin_amdgcn_s_barrier();          // un-stagger
     MAEST_WAIT_VMCNT(0);   // drain the past-the-end loads before LDS is reused
     __syncthreads();       // LDS becomes the C staging area
-#if defined(MAEST_ABLATE_NO_EPILOGUE) || defined(MAEST_ABLATE_ROLLING)
-    // timing experiments: no C-tile epilogue at all (results are not stored); the accumulators are kept alive
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < MTW; ++j) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" :: "v"(acc[i][j]));
-#endif
-        }
-    return;
-#endif
     if constexpr (MTW == 2) {
         if (p.out_dtype == MAEST_BF16) epilogueH<2, sizeof(T) == 4>(smem, acc, p, m0, n0, wm, wn, lane, tid);
         else epilogueH<4, sizeof(T) == 4>(smem, acc, p, m0, n0, wm, wn, lane, tid);
@@ -923,22 +845,16 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTn256Params p) {
         const char* lb = la + G2_TILE;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-#ifdef MAEST_ABLATE_NO_DSREAD
-            if (s > 0) continue;
-#endif
 #pragma unroll
             for (int a = 0; a < 4; ++a) fa[ks][a] = frag_tn256<T>(la, ks, wm * 128 + a * 32, lane);
 #pragma unroll
             for (int b = 0; b < 2; ++b) fb[ks][b] = frag_tn256<T>(lb, ks, wn * 64 + b * 32, lane);
         }
-#ifndef MAEST_ABLATE_NO_DMA
         issue(s + 3);   // (in the LOAD phase: spread between the MFMAs of COMPUTE it measured 9 % slower here)
-#endif
         __builtin_amdgcn_s_waitcnt(0x0078);   // vmcnt(8) lgkmcnt(0)
         __builtin_amdgcn_s_barrier();
         tn_pin(fa, fb);
         __builtin_amdgcn_s_setprio(1);
-#ifndef MAEST_ABLATE_NO_MFMA
         if constexpr (X3) {     // split-bf16: the two k chunks of a slice feed one K = 16 MFMA triple
 #pragma unroll
             for (int a = 0; a < 4; ++a)
@@ -953,12 +869,6 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTn256Params p) {
                 for (int b = 0; b < 2; ++b) mma_chunk<T>(acc[a][b], fa[ks][a], fb[ks][b]);   // D rows = i, cols = j
         }
         }
-#else
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) acc[a][0][ks] += u2f(fa[ks][a][0] ^ fb[ks][a & 1][1]);
-#endif
         __builtin_amdgcn_s_setprio(0);
         if (do_colsum) {   // the fragments already hold A[k][i] for (i = lane&31, 8 or 4 k's): sum them on the VALU
             if (cs_turn == 0) {
@@ -983,9 +893,6 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTn256Params p) {
     if (wm == 0) __builtin_amdgcn_s_barrier();
     MAEST_WAIT_VMCNT(0);
 
-#ifdef MAEST_ABLATE_NO_EPI
-    if (acc[0][0][0] != 123.456f) return;
-#endif
     if (p.ws != nullptr) {
         // Workspace form of the split-K combine (end of round 3).  The atomic form below issues 1024 global_atomic_add_f32 per
         // workgroup, 256 B each, and an fp32 atomic instruction takes ~50 ns of a CU's store path (scratch/probe/store_issue.hip):

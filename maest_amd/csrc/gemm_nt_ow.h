@@ -33,20 +33,6 @@ constexpr int OW_BIAS0 = 2 * 33792;           // the bias row's place in the C s
 #else
 #define OW_DEV 0
 #endif
-#ifndef OW_ABLATE
-#define OW_ABLATE 0       // timing experiments only (results wrong on purpose): bit 0 no LDS-DMA requests, 1 no barrier / vmcnt wait,
-#endif                    // 2 no MFMAs, 3 no fragment reads, 4 no epilogue, 5 every workgroup loads tile 0, 7 plain instead of streaming C stores
-
-// OW_PROF: timing instrumentation only (scratch/ow_prof.py builds a second library with it; never defined in the product build):
-// shader-clock time the four waves of workgroup 5 spend in each part of a stage, summed over the tile.
-#ifdef OW_PROF
-#ifdef OW_PROF_VAR
-__device__ unsigned long long* g_ow_prof = nullptr;
-#endif
-#define OW_TICK(slot) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); c.prof[slot] += (unsigned)(t_ - c.tprev); c.tprev = t_; } while (0)
-#else
-#define OW_TICK(slot) ((void)0)
-#endif
 
 // The fragment and bias registers (OW_FRAGS) and the whole accumulator half (OW_ACCS) as clobber lists: OW_FRAGS on every main-loop statement,
 // OW_ACCS on the waits and barriers only (two or three statements per stage keep hipcc from parking a value there across the loop; on every
@@ -60,10 +46,6 @@ struct OwCtx {
                                  // 16-row block go into the read's immediate offset: nothing per stage is left to compute)
     uint32_t lds0;               // LDS address of the dynamic segment
     int wave;                    // (wave-uniform)
-#ifdef OW_PROF
-    unsigned prof[24];
-    unsigned long long tprev;
-#endif
 #if !OW_DEV
     f32x4_t acc[8][8];           // (host emulator: the state the device keeps in owned registers) [n16][m16]
     chunk16 fa[2][8], fb[2][8];
@@ -106,7 +88,6 @@ template <int SET, int N16, int M16, bool ZERO>
 __device__ __forceinline__ void ow_slot_plain(OwCtx& c) {
 #if OW_DEV
     constexpr int D = 4 * (8 * N16 + M16), A = OW_V_F + 64 * SET + 4 * M16, B = OW_V_F + 64 * SET + 32 + 4 * N16;
-    if (OW_ABLATE & 4) return;
     if constexpr (ZERO) asm volatile(OW_MFMA_ZERO : : "i"(D), "i"(B), "i"(A) : OW_FRAGS);
     else asm volatile(OW_MFMA_ACC : : "i"(D), "i"(B), "i"(A) : OW_FRAGS);
 #else
@@ -118,9 +99,6 @@ __device__ __forceinline__ void ow_slot_read(OwCtx& c, uint32_t addr) {
 #if OW_DEV
     constexpr int D = 4 * (8 * N16 + M16), A = OW_V_F + 64 * SET + 4 * M16, B = OW_V_F + 64 * SET + 32 + 4 * N16;
     constexpr int V = OW_V_F + 64 * RSET + (ISB ? 32 : 0) + 4 * T;
-    if ((OW_ABLATE & 12) == 12) return;
-    if (OW_ABLATE & 8) { ow_slot_plain<SET, N16, M16, ZERO>(c); return; }
-    if (OW_ABLATE & 4) { asm volatile("ds_read_b128 v[%c1:%c1+3], %0 offset:%c2" : : "v"(addr), "i"(V), "i"(OFF + T * 2048) : OW_FRAGS); return; }
     if constexpr (ZERO)
         asm volatile(OW_MFMA_ZERO "\n\tds_read_b128 v[%c4:%c4+3], %3 offset:%c5" : : "i"(D), "i"(B), "i"(A), "v"(addr), "i"(V), "i"(OFF + T * 2048) : OW_FRAGS);
     else
@@ -134,12 +112,7 @@ template <int SET, int N16, int M16, bool ZERO, int DST>
 __device__ __forceinline__ void ow_slot_dma(OwCtx& c, const char* base, uint32_t& voff, uint32_t piece0) {
 #if OW_DEV
     constexpr int D = 4 * (8 * N16 + M16), A = OW_V_F + 64 * SET + 4 * M16, B = OW_V_F + 64 * SET + 32 + 4 * N16;
-    if (OW_ABLATE & 1) { ow_slot_plain<SET, N16, M16, ZERO>(c); return; }
     const uint32_t lds = __builtin_amdgcn_readfirstlane(piece0);
-    if (OW_ABLATE & 4) {
-        asm volatile("s_add_u32 m0, %2, %c3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\tv_add_u32 %0, 0x80, %0" : "+v"(voff) : "s"(base), "s"(lds), "i"(DST) : "memory", "scc", OW_FRAGS);
-        return;
-    }
     if constexpr (ZERO)
         asm volatile("s_add_u32 m0, %2, %c3\n\t" "v_mfma_f32_16x16x32_" MAEST_T16 " a[%c4:%c4+3], v[%c5:%c5+3], v[%c6:%c6+3], 0" "\n\tglobal_load_lds_dwordx4 %0, %1\n\tv_add_u32 %0, 0x80, %0"
                      : "+v"(voff) : "s"(base), "s"(lds), "i"(DST), "i"(D), "i"(B), "i"(A) : "memory", "scc", OW_FRAGS);
@@ -157,7 +130,6 @@ __device__ __forceinline__ void ow_slot_dma(OwCtx& c, const char* base, uint32_t
 template <int DST>               // DST: byte offset of the piece from the wave's first piece of ring buffer 0 (`piece0`, an SGPR)
 __device__ __forceinline__ void ow_dma(const char* base, uint32_t& voff, uint32_t piece0, OwCtx& c) {
 #if OW_DEV
-    if (OW_ABLATE & 1) return;
     const uint32_t lds = __builtin_amdgcn_readfirstlane(piece0);
     asm volatile("s_add_u32 m0, %2, %c3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\tv_add_u32 %0, 0x80, %0"
                  : "+v"(voff) : "s"(base), "s"(lds), "i"(DST) : "memory", "scc", OW_FRAGS);
@@ -172,8 +144,7 @@ template <int SET, int T, bool ISB, int OFF = 0>
 __device__ __forceinline__ void ow_read(OwCtx& c, uint32_t addr) {
 #if OW_DEV
     constexpr int V = OW_V_F + 64 * SET + (ISB ? 32 : 0) + 4 * T;
-    if (!(OW_ABLATE & 8))
-        asm volatile("ds_read_b128 v[%c1:%c1+3], %0 offset:%c2" : : "v"(addr), "i"(V), "i"(OFF + T * 2048) : OW_FRAGS);
+    asm volatile("ds_read_b128 v[%c1:%c1+3], %0 offset:%c2" : : "v"(addr), "i"(V), "i"(OFF + T * 2048) : OW_FRAGS);
 #else
     ow_read_twin<SET, T, ISB>(c, addr, OFF);
 #endif
@@ -181,7 +152,6 @@ __device__ __forceinline__ void ow_read(OwCtx& c, uint32_t addr) {
 template <int N>
 __device__ __forceinline__ void ow_wait_vm() {       // all but this wave's N newest LDS-DMA requests have landed
 #if OW_DEV
-    if (OW_ABLATE & 2) return;
     asm volatile("s_waitcnt vmcnt(%c0)" : : "i"(N) : "memory", OW_FRAGS);
 #endif
 }
@@ -192,7 +162,6 @@ __device__ __forceinline__ void ow_wait_lds() {      // every fragment read this
 }
 __device__ __forceinline__ void ow_barrier() {
 #if OW_DEV
-    if (OW_ABLATE & 2) return;
     asm volatile("s_barrier" : : : "memory", OW_FRAGS, OW_ACCS);
 #else
     __syncthreads();

@@ -47,7 +47,6 @@ int gemm_nt256o_launch(Gemm256Params&, hipStream_t) {
 }  // namespace maest
 #else
 
-#define OW_PROF_VAR 1       // (this file defines the profiling variable of OW_PROF builds)
 #include "gemm_nt_ow.h"     // the ring, the register map and the main-loop statements 
 
 namespace maest {
@@ -190,10 +189,7 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
             }
             // streaming output: written once, re-read by a later kernel after > L2-size of other traffic
             if (full || m0 + r0 + ro0 + i * RS < p.M)
-            {
-                if (OW_ABLATE & 128) *reinterpret_cast<chunk16*>(dthr + (ro0 + i * RS) * drow) = o;       // (A/B: plain instead of streaming stores)
-                else __builtin_nontemporal_store(o, reinterpret_cast<chunk16*>(dthr + (ro0 + i * RS) * drow));
-            }
+                __builtin_nontemporal_store(o, reinterpret_cast<chunk16*>(dthr + (ro0 + i * RS) * drow));
         }
     };
     auto drain = [&](int ps, const char* buf) {
@@ -224,39 +220,27 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
     if (MODE == 0) request_next();
     if (MODE != 0) prefetch(0);
     stage(integral_constant<int, 0>{}, smem);
-    OW_TICK(13);
     sync();
-    OW_TICK(14);
     drain(0, smem);
-    OW_TICK(15);
     if (MODE != 0) prefetch(1);
     sync();
     stage(integral_constant<int, 1>{}, smem);
-    OW_TICK(13);
     sync();
-    OW_TICK(14);
     drain(1, smem);
-    OW_TICK(15);
     if (MODE != 0) prefetch(2);
     sync();
     stage(integral_constant<int, 2>{}, smem);
-    OW_TICK(13);
     sync();
-    OW_TICK(14);
     drain(2, smem);
-    OW_TICK(15);
     if (MODE != 0) prefetch(3);
     sync();
     stage(integral_constant<int, 3>{}, smem);
-    OW_TICK(13);
     sync();
-    OW_TICK(14);
     if (MODE != 0) {
         consume_aux();
         request_next();
     }
     drain(3, smem);
-    OW_TICK(15);
 }
 // One kernel per epilogue form (OSZ: bytes per output element; GMODE / MODE as above): the launcher picks.  (All forms inlined into one
 // persistent kernel made hipcc hoist every form's loop invariants in front of the tile loop and spill them -- into the accumulator half.)
@@ -325,8 +309,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
     const char* bbase = nullptr;
     uint32_t voa[8], vob[8];
     auto set_sources = [&](int tm0, int tn0) {
-        abase = p.A + ((OW_ABLATE & 32) ? 0 : (int64_t)tm0 * p.lda * 2);      // (bit 5: every workgroup loads tile 0)
-        bbase = p.B + ((OW_ABLATE & 32) ? 0 : (int64_t)tn0 * p.ldb * 2);
+        abase = p.A + (int64_t)tm0 * p.lda * 2;
+        bbase = p.B + (int64_t)tn0 * p.ldb * 2;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int r = (wave * 8 + i) * 8 + (lane >> 3);
@@ -346,11 +330,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
         ow_dma<BUF * OW_UNIT + 6 * 1024>(base, vo[6], piece0, c); ow_dma<BUF * OW_UNIT + 7 * 1024>(base, vo[7], piece0, c);
     };
     using std::integral_constant;
-#ifdef OW_PROF
-    for (int i = 0; i < 24; ++i) c.prof[i] = 0;
-    c.tprev = __builtin_amdgcn_s_memtime();
-    const unsigned long long t_begin = c.tprev;
-#endif
     int v = blockIdx.x, m0, n0;
     tile_of(v, m0, n0);
     set_sources(m0, n0);
@@ -380,7 +359,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
     const float* bias_src = p.bias != nullptr ? p.bias + n0 + 4 * lane : nullptr;
     const uint32_t bias_dst = c.lds0 + (uint32_t)(OW_EPI0 + OW_BIAS0 + lane * 16);
     ow_bias_load(c, bias_src);
-    OW_TICK(10);                      // (prologue)
     // Stage j = two k32 halves of 64 MFMAs.  Half 0 multiplies fragment set 0 (read during the previous stage's half 1) and reads set 1 =
     // the stage's second k32 half; half 1 multiplies set 1 and reads set 0 = the NEXT stage's first half (the last stage reads the ring's next
     // buffers there: stale bytes nobody multiplies).  The stage's one barrier b_j stands BETWEEN the halves: in front of it every wave has read
@@ -398,17 +376,11 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
         constexpr int ABUF = (2 * PH) % 5, BBUF = (2 * PH + 1) % 5, ABUF_N = (2 * PH + 2) % 5, BBUF_N = (2 * PH + 3) % 5;
         constexpr int BBUF_P = (2 * PH + 4) % 5;             // B_{j-1}'s buffer
         constexpr int ND = KIND == 2 ? 4 : 0;
-        OW_TICK(0);
         ow_wait_lds();                // set 0 is in the registers
-        OW_TICK(1);
         ow_half<0, FIRST, ABUF, BBUF, 1, ND, 0, BBUF_P, 4, BBUF_P>(c, abase, voa, abase, voa, piece0);
-        OW_TICK(2);
         ow_wait_lds();                // set 1 is in the registers (its reads are >= 16 slots old)
-        OW_TICK(3);
         ow_wait_vm<(KIND == 2 ? 8 : 0)>();
-        OW_TICK(8);
         ow_barrier();                 // b_j
-        OW_TICK(9);
         ow_half<1, false, ABUF_N, BBUF_N, 0, ND, 0, ABUF, 4, ABUF>(c, bbase, vob, bbase, vob, piece0);
     };
     // stages [j, jend) starting at ring phase ph (= j % 5), all of one kind; steady state: a counter, a compare, a branch not taken
@@ -431,7 +403,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
         run(integral_constant<int, 0>{}, j, nstages, ph);
     }
 
-    OW_TICK(0);                       // (the last half 1 counts as slot 0 of the next stage)
     ow_wait_vm<0>();
     ow_wait_lds();
     ow_barrier();                     // the ring is drained and read: LDS becomes the C staging area
@@ -439,10 +410,8 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
     ow_wait_lds();
     ow_barrier();
 #if OW_DEV
-    if (OW_ABLATE & 16) return;
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7");      // the last MFMAs' results are in the accumulator registers
 #endif
-    OW_TICK(11);                      // (drain)
     const int vn = v + (int)gridDim.x;
     const bool more = vn < nwg;       // (wave-uniform)
     int m0n = 0, n0n = 0;
@@ -462,17 +431,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
     asm volatile("" : "+s"(wave_e));
 #endif
     ow_epilogue_run<OSZ, GMODE, MODE>(smem, c, p, m0, n0, wave_e >> 1, wave_e & 1, tid_e & 63, tid_e, request_next);
-#ifdef OW_PROF
-    if (v == (int)blockIdx.x) {       // (the workgroup's first tile)
-        OW_TICK(12);
-        if ((blockIdx.x == 5 || blockIdx.x == gridDim.x - 3) && g_ow_prof != nullptr && lane == 0) {
-            unsigned long long* out = g_ow_prof + (blockIdx.x == 5 ? 0 : 96);
-            for (int i = 0; i < 22; ++i) out[wave * 24 + i] = c.prof[i];
-            out[wave * 24 + 22] = t_begin;
-            out[wave * 24 + 23] = c.tprev;
-        }
-    }
-#endif
     if (!more) break;
     v = vn;
     m0 = m0n;
@@ -481,9 +439,6 @@ __global__ __launch_bounds__(256, 1) void gemm_nt256o_kernel(Gemm256Params p) {
     ow_sync_epilogue();               // every wave has read the last pass out of the staging area: A_1 / B_1 may be requested into it
     }
 }
-#ifdef OW_PROF
-extern "C" int maest_debug_ow_prof(void* p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_ow_prof), &p, sizeof(p)); }
-#endif
 
 template <int OSZ, int GMODE, int MODE>
 static int launch256o(Gemm256Params& p, hipStream_t stream) {

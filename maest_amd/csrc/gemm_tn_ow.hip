@@ -52,9 +52,6 @@ constexpr int TW_V_LO = 176, TW_V_HI = 255;   // (the audited range)
 #else
 #define TW_DEV 0
 #endif
-#ifndef TW_ABLATE
-#define TW_ABLATE 0       // timing experiments only (results wrong on purpose): bit 0 no LDS-DMA requests, 1 no barrier / vmcnt wait,
-#endif                    // 2 no MFMAs, 3 no fragment reads, 4 no epilogue
 
 // The owned arch VGPRs (TW_FRAGS, on every main-loop statement) and the whole accumulator half (TW_ACCS, on the waits and barriers) as
 // clobber lists: hipcc cannot keep a value in them across the main loop (gemm_nt_ow.hip has the story), and may use v176 .. v255 behind it.
@@ -77,8 +74,7 @@ template <int SET, int T, bool ISB, int HF, int KS>
 __device__ __forceinline__ void tw_read(TwCtx& c, uint32_t addr) {
 #if TW_DEV
     constexpr int V = TW_V_F + 32 * SET + (ISB ? 16 : 0) + 4 * T + 2 * HF;
-    if (!(TW_ABLATE & 8))
-        asm volatile("ds_read_b64_tr_b16 v[%c1:%c2], %0 offset:%c3" : : "v"(addr), "i"(V), "i"(V + 1), "i"(KS * 8192 + HF * 2048) : TW_FRAGS);
+    asm volatile("ds_read_b64_tr_b16 v[%c1:%c2], %0 offset:%c3" : : "v"(addr), "i"(V), "i"(V + 1), "i"(KS * 8192 + HF * 2048) : TW_FRAGS);
 #else
     typedef short v4i16_t __attribute__((ext_vector_type(4)));
     const v4i16_t r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) v4i16_t*)(c.lds + addr + KS * 8192 + HF * 2048));
@@ -93,7 +89,6 @@ template <int SET, int A, int B, bool ZERO>
 __device__ __forceinline__ void tw_mfma(TwCtx& c) {
 #if TW_DEV
     constexpr int D = 16 * (4 * A + B), FA = TW_V_F + 32 * SET + 4 * A, FB = TW_V_F + 32 * SET + 16 + 4 * B;
-    if (TW_ABLATE & 4) return;
     if constexpr (ZERO)
         asm volatile("v_mfma_f32_32x32x16_" MAEST_T16 " a[%c0:%c1], v[%c2:%c3], v[%c4:%c5], 0"
                      : : "i"(D), "i"(D + 15), "i"(FA), "i"(FA + 3), "i"(FB), "i"(FB + 3) : TW_FRAGS);
@@ -111,7 +106,6 @@ __device__ __forceinline__ void tw_mfma(TwCtx& c) {
 // One LDS-DMA request (1 KiB = 2 token rows x 512 B); voff then moves on by one slice (`step` bytes, wave-uniform)
 __device__ __forceinline__ void tw_dma(const char* base, uint32_t& voff, uint32_t step, uint32_t dst, TwCtx& c) {
 #if TW_DEV
-    if (TW_ABLATE & 1) return;
     const uint32_t lds = __builtin_amdgcn_readfirstlane(dst);
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1\n\tv_add_u32 %0, %3, %0"
                  : "+v"(voff) : "s"(base), "s"(lds), "s"(step) : "memory", TW_FRAGS);
@@ -125,10 +119,9 @@ template <int VM, int LGKM>
 __device__ __forceinline__ void tw_wait() {          // VM / LGKM < 0: that counter is not waited for
 #if TW_DEV
     if constexpr (VM >= 0 && LGKM >= 0) {
-        if (TW_ABLATE & 2) asm volatile("s_waitcnt lgkmcnt(%c0)" : : "i"(LGKM) : "memory", TW_FRAGS, TW_ACCS);
-        else asm volatile("s_waitcnt vmcnt(%c0) lgkmcnt(%c1)" : : "i"(VM), "i"(LGKM) : "memory", TW_FRAGS, TW_ACCS);
+        asm volatile("s_waitcnt vmcnt(%c0) lgkmcnt(%c1)" : : "i"(VM), "i"(LGKM) : "memory", TW_FRAGS, TW_ACCS);
     } else if constexpr (VM >= 0) {
-        if (!(TW_ABLATE & 2)) asm volatile("s_waitcnt vmcnt(%c0)" : : "i"(VM) : "memory", TW_FRAGS, TW_ACCS);
+        asm volatile("s_waitcnt vmcnt(%c0)" : : "i"(VM) : "memory", TW_FRAGS, TW_ACCS);
     } else {
         asm volatile("s_waitcnt lgkmcnt(%c0)" : : "i"(LGKM) : "memory", TW_FRAGS, TW_ACCS);
     }
@@ -136,7 +129,6 @@ __device__ __forceinline__ void tw_wait() {          // VM / LGKM < 0: that coun
 }
 __device__ __forceinline__ void tw_barrier() {
 #if TW_DEV
-    if (TW_ABLATE & 2) return;
     asm volatile("s_barrier" : : : "memory", TW_FRAGS, TW_ACCS);
 #else
     __syncthreads();
@@ -408,7 +400,6 @@ __global__ __launch_bounds__(256, 1) void gemm_tn256o_kernel(GemmTn256Params p) 
     }
     tw_wait<0, 0>();
 #if TW_DEV
-    if (TW_ABLATE & 16) return;
     asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7");      // the last MFMAs' results are in the accumulator registers
 #endif
     // split-K partial -> C by fp32 atomics, as the accumulator layout has them (a half-wave = 32 consecutive columns of one row)
