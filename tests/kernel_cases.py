@@ -868,36 +868,74 @@ EDGE_VALUES = [0.0, -0.0, 1.0, -1.0, 65504.0, -65504.0, 65519.99, -65519.99, 655
                6.0e-5, -3.0e-5, 1.0e-5, 1.0e-6, -1.0e-7, 5.96e-8, 2.9802322e-8, 2.99e-8, 1.0e-8, 2049.0, 2051.0, 1.0009765625, 0.33333334]
 
 
+# ... and at bfloat16's: round-to-even ties at the 8-bit boundary (1 + 2^-8 -> 1, 1 + 3 * 2^-8 -> 1 + 2^-6, 257 -> 256, 259 -> 260) and
+# their neighbours, the largest finite bf16 (3.3895e38 = MAX_BF16; MAX_BF16 + 2^119 = 3.3962e38 is the tie that rounds to inf) up to
+# the largest fp32, the smallest normal (1.1755e-38) and the subnormal range -- fp32's own -- down to bf16's smallest step
+# 2^-133 = 9.1835e-41, the tie 2^-134 below it (to even: 0) and fp32's smallest step
+MAX_BF16 = (2.0 - 2.0 ** -7) * 2.0 ** 127
+EDGE_VALUES_BF16 = [0.0, -0.0, 1.0, -1.0, 1.0 + 2.0 ** -8, 1.0 + 2.0 ** -8 + 2.0 ** -23, 1.0 + 2.0 ** -8 - 2.0 ** -23, -(1.0 + 3 * 2.0 ** -8),
+                    257.0, 259.0, -257.0, 258.5, MAX_BF16, -MAX_BF16, MAX_BF16 + 2.0 ** 119, -(MAX_BF16 + 2.0 ** 119),
+                    MAX_BF16 + 2.0 ** 119 - 2.0 ** 104, 3.4e38, 3.4028234e38, -3.4028234e38, 2.0 ** -126, -(2.0 ** -126), 1.0e-38, -7.0e-39,
+                    2.0 ** -127, 1.0e-40, 2.0 ** -133, -(2.0 ** -133), 2.0 ** -134, 2.0 ** -134 + 2.0 ** -149, 3 * 2.0 ** -134, 1.0e-41, 2.0 ** -149,
+                    0.33333334]
+
+
+def _bits_equal(got, want_f32, what):
+    """`got` (a 16-bit container of the calling thread's build) holds exactly lp(want_f32): torch's .half() in the half build, torch's
+    .bfloat16() in the bf16 build -- round to nearest even, +-inf past the tie above the largest finite value, subnormals kept (not
+    flushed).  NaN compared as NaN."""
+    if f16_build():
+        return _half_bits_equal(got, want_f32, what)
+    g = got.detach().cpu().view(torch.int16)
+    w = want_f32.detach().cpu().bfloat16().view(torch.int16)
+    same = (g == w) | (torch.isnan(want_f32.cpu()) & torch.isnan(got.detach().cpu().float()))
+    if not bool(same.all()):
+        i = tuple(int(v) for v in (~same).nonzero()[0])
+        raise AssertionError(f"{what}: {int((~same).sum())} values differ from torch's .bfloat16(); first at {i}: fp32 {float(want_f32.cpu()[i])!r} -> "
+                             f"{float(got.detach().cpu().float()[i])!r}, want {float(want_f32.cpu()[i].bfloat16())!r}")
+
+
 def edge_values(shape, seed):
-    """[shape] fp32: EDGE_VALUES first, then magnitudes log-uniform over 1e-9 .. 1e6 with random signs."""
+    """[shape] fp32: the edge values of the calling thread's 16-bit format first (EDGE_VALUES / EDGE_VALUES_BF16), then magnitudes
+    log-uniform over 1e-9 .. 1e6 (half) / 1e-44 .. 3e38 (bf16) with random signs."""
     rng = np.random.Generator(np.random.PCG64(seed))
     n = int(np.prod(shape))
-    v = np.exp(rng.uniform(np.log(1e-9), np.log(1e6), n)) * rng.choice([-1.0, 1.0], n)
-    v[: len(EDGE_VALUES)] = EDGE_VALUES
+    edges, lo, hi = (EDGE_VALUES, 1e-9, 1e6) if f16_build() else (EDGE_VALUES_BF16, 1e-44, 3e38)
+    v = np.exp(rng.uniform(np.log(lo), np.log(hi), n)) * rng.choice([-1.0, 1.0], n)
+    v[: len(edges)] = edges
     return torch.from_numpy(v.astype(np.float32)).reshape(shape)
 
 
 def case_half_conversions(dev, M=512, N=256, K=64, forms=({},)):
-    """Half build: every fp32 -> 16-bit conversion of cast_weights(_multi), cast_rows and a GEMM's 16-bit output equals torch's .half()
-    bit for bit.  The GEMM's fp32 results are chosen: out[m, n] = x[m] * 1 + bias[n] with x half values (0, +-65504, 65472, the smallest
-    normal, ...) and fp32 biases, so that the sums straddle 65504 and fill the subnormal range; `forms`: ops.options of the kernels to
-    take (each its own epilogue conversion)."""
-    assert f16_build()
+    """Every fp32 -> 16-bit conversion of cast_weights(_multi), cast_rows and a GEMM's 16-bit output equals lp() of the fp32 value -- in
+    the half build torch's .half(), in the bf16 build torch's .bfloat16() -- bit for bit.  The GEMM's fp32 results are chosen:
+    out[m, n] = x[m] * 1 + bias[n] with x 16-bit values (0, +- the largest finite one and its neighbour, the smallest normal, ...) and fp32
+    biases, so that the sums straddle the largest finite value, sit on round-to-even ties and fill the subnormal range; `forms`:
+    ops.options of the kernels to take (each its own epilogue conversion)."""
     w = edge_values((70, 130), 300)
     d, dt_ = ops.cast_weights(w.to(dev), torch.bfloat16, want=True, want_t=True)
-    _half_bits_equal(d, w, "cast_weights")
-    _half_bits_equal(dt_, w.t(), "cast_weights transposed")
+    _bits_equal(d, w, "cast_weights")
+    _bits_equal(dt_, w.t(), "cast_weights transposed")
     ws = [edge_values((64, 256), 301), edge_values((33, 70), 302)]      # the quad path and the element-wise one
     for t, (o, ot) in zip(ws, ops.cast_weights_multi([t.to(dev) for t in ws], torch.bfloat16, want=True, want_t=True)):
-        _half_bits_equal(o, t, "cast_weights_multi")
-        _half_bits_equal(ot, t.t(), "cast_weights_multi transposed")
+        _bits_equal(o, t, "cast_weights_multi")
+        _bits_equal(ot, t.t(), "cast_weights_multi transposed")
     r = ops.cast_rows(w.to(dev), torch.bfloat16, ld_dst=192)
-    _half_bits_equal(r[:, :130], w, "cast_rows")
+    _bits_equal(r[:, :130], w, "cast_rows")
     assert not r[:, 130:].view(torch.int16).any(), "cast_rows pad must be zero"
-    xs = torch.tensor([0.0, 65504.0, -65504.0, 65472.0, 1.0, -1.0, 6.1035156e-5, -3.0517578e-5, 0.5, 1024.0, 65440.0, -65472.0])
+    if f16_build():
+        xs = torch.tensor([0.0, 65504.0, -65504.0, 65472.0, 1.0, -1.0, 6.1035156e-5, -3.0517578e-5, 0.5, 1024.0, 65440.0, -65472.0])
+        bs = torch.tensor([0.0, 16.0, 15.99, 31.99, 32.0, 47.99, 48.0, -16.0, -15.99, 1.0e-7, -1.0e-7, 5.0e-8, 3.0e-8, 6.0e-5, 1.0e-5, 7.0e4])
+        small = 1e-3
+    else:
+        # (MAX_BF16 + 2^119 is the tie to inf; 1 + 2^-8 and 1 + 3 * 2^-8 the ties to 1 and to 1 + 2^-6; 256 + 1 / + 3 those at 256)
+        u = 2.0 ** 119
+        xs = torch.tensor([0.0, MAX_BF16, -MAX_BF16, MAX_BF16 - 2 * u, 1.0, -1.0, 2.0 ** -126, -(2.0 ** -127), 0.5, 256.0, 2.0 ** -133, -256.0])
+        bs = torch.tensor([0.0, u, 0.999 * u, 1.001 * u, 3 * u, -u, -0.999 * u, 2.0 ** -8, 3 * 2.0 ** -8, 2.0 ** -8 + 2.0 ** -20, -(2.0 ** -8), 1.0, 3.0,
+                           1.0e-40, -1.0e-40, 2.0 ** -134, 4.7e-41, 1.0e-38, -5.0e-39, 3.4e38])
+        small = 1e-37
     x = torch.where(torch.arange(M) < 2 * len(xs), xs[torch.arange(M) % len(xs)], 0.0)     # (the rest: +0 + bias)
-    bs = torch.tensor([0.0, 16.0, 15.99, 31.99, 32.0, 47.99, 48.0, -16.0, -15.99, 1.0e-7, -1.0e-7, 5.0e-8, 3.0e-8, 6.0e-5, 1.0e-5, 7.0e4])
-    bias = torch.cat([bs, edge_values((N - len(bs),), 303) * 1e-3])
+    bias = torch.cat([bs, edge_values((N - len(bs),), 303) * small])
     a = torch.zeros(M, K)
     a[:, 0] = x
     b = torch.zeros(N, K)
@@ -906,7 +944,7 @@ def case_half_conversions(dev, M=512, N=256, K=64, forms=({},)):
     for kw in forms:
         with ops.options(**kw):
             c = ops.gemm_nt(lp(a).to(dev), lp(b).to(dev), bias.to(dev), out_dtype=torch.bfloat16)
-        _half_bits_equal(c, want, f"gemm 16-bit output {kw}")
+        _bits_equal(c, want, f"gemm 16-bit output {kw}")
 
 
 def _finite_except(t, bad, what):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from maest_amd import _lib, ops
+from tests import attention_cases as AC
 from tests import kernel_cases as KC
 from tests.test_emu_grad_kernels import _case, _im2col_ref, _stripes
 
@@ -96,6 +97,27 @@ def test_emu_f16_attention_prescaled_q(emu16):
 def test_emu_f16_attention_restricted_to_the_head_tokens(emu16, B, N):
     """q_rows = 2 forward / backward and gather_head_rows / scatter_head_rows."""
     KC.controlled(KC.case_attention_head_rows, emu16, BF, B, N)
+
+
+@pytest.mark.parametrize("B,N,kw", [(1, 75, {}), (2, 40, {}), (1, 40, {"qs": True}), (2, 40, {"q_rows": 2})])
+def test_emu_f16_attention_calibrated(emu16, B, N, kw):
+    """Every forward and backward form of the half build inside 1.25 x (rms) / 2 x (max) of the error its own half roundings make (the forms
+    left to the device: test_emu_kernels.py, test_emu_attention_calibrated)."""
+    with _lib.flavour("f16"):
+        AC.case_attention_calibrated(emu16, B, N, **kw)
+
+
+@pytest.mark.parametrize("B,N,qs", [(1, 75, False), (2, 40, False), (1, 40, True)])
+def test_emu_f16_attention_exact(emu16, B, N, qs):
+    """A forward whose every softmax term is a power of two: each form within one half ulp of the exactly known answer."""
+    with _lib.flavour("f16"):
+        AC.case_attention_exact(emu16, B, N, qs=qs)
+
+
+def test_emu_f16_attention_exact_rescale_paths(emu16):
+    """The exact forward with the levels that send the persistent kernel's twin down pw_softmax_slow, in the half build."""
+    with _lib.flavour("f16"):
+        AC.case_attention_exact(emu16, 1, 75, hot=True)
 
 
 @pytest.mark.parametrize("mix", [False, True])

@@ -4,6 +4,7 @@ bookkeeping, tail masking and barrier placement -- not timing."""
 import pytest
 import torch
 
+from tests import attention_cases as AC
 from tests import kernel_cases as KC
 
 DT = [torch.float32, torch.bfloat16]
@@ -143,6 +144,37 @@ def test_emu_attention_persistent_forward(emu):
     ref, ref_lse = K._attn_ref(qkv.float(), 1, 130, 0.125)
     K.close(out, ref, 2e-2, 2e-2, "persistent attention forward (emulated)")
     K.close(lse, ref_lse, 1e-4, 2e-2, "persistent attention forward lse (emulated)")
+
+
+CALIBRATED = [(1, 75, {}), (2, 40, {}), (1, 40, {"qs": True}), (2, 40, {"q_rows": 2})]
+
+
+@pytest.mark.parametrize("B,N,kw", CALIBRATED)
+def test_emu_attention_calibrated(emu, B, N, kw):
+    """Every bf16 forward and backward form inside 1.25 x (rms) / 2 x (max) of the error its own 16-bit roundings make (tests/attention_cases.py):
+    two key tiles, two clips, the pre-scaled q contract, the rows restricted to the head tokens.  Not run here, for the emulator's seconds
+    per launch: the register-staged two-kernel backward (attn_bwd = 4), which case_attention ties bit for bit to the LDS-DMA form that is
+    run, the wave counts 5 / 6 / 8, and the four-wave LDS-DMA forward a second time by its option (it is the default at these N); the
+    device tests run them all."""
+    AC.case_attention_calibrated(emu, B, N, **kw)
+
+
+@pytest.mark.parametrize("B,N,qs", [(1, 75, False), (2, 40, False), (1, 40, True)])
+def test_emu_attention_exact(emu, B, N, qs):
+    """A forward whose every softmax term is a power of two: each form within one bf16 ulp of the exactly known answer."""
+    AC.case_attention_exact(emu, B, N, qs=qs)
+
+
+def test_emu_attention_exact_rescale_paths(emu):
+    """... with the levels that send the persistent kernel's twin down pw_softmax_slow: a half-row sum below 1e-30 on the first tile, above
+    4096 on the first and on the second."""
+    AC.case_attention_exact(emu, 1, 75, hot=True)
+
+
+def test_emu_bf16_conversions_round_like_torch(emu, gemm_options):
+    """cast_weights(_multi), cast_rows and a GEMM's bf16 output (the 128 x 128 kernel, and the one-wave-per-SIMD kernel's twin) against torch's
+    .bfloat16() bit for bit: round to nearest even, +-inf past 3.3962e38, subnormals kept."""
+    KC.case_half_conversions(emu, M=512, N=256, K=64, forms=({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}))
 
 
 def test_emu_split_bf16_products(emu):

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from maest_amd import _lib
+from tests import attention_cases as AC
 from tests import kernel_cases as KC
 
 pytestmark = pytest.mark.gpu
@@ -102,6 +103,30 @@ def test_f16_attention_prescaled_q(BN):
 @pytest.mark.parametrize("BN", [(3, 290), (2, 560)])
 def test_f16_attention_restricted_to_the_head_tokens(BN):
     KC.controlled(KC.case_attention_head_rows, DEV, BF, *BN)
+
+
+@pytest.mark.parametrize("B,N,kw", [(1, 64, {}), (1, 129, {}), (3, 281, {}), (24, 290, {}), (24, 290, {"qs": True}), (2, 321, {}), (2, 560, {}),
+                                    (13, 875, {}), (3, 290, {"q_rows": 2})])
+def test_f16_attention_calibrated(B, N, kw):
+    """Every forward and backward form of the half build inside 1.25 x (rms) / 2 x (max) of the error its own half roundings make (the
+    shapes of test_kernels_gpu.py: test_attention_calibrated)."""
+    with _lib.flavour("f16"):
+        AC.case_attention_calibrated(DEV, B, N, **kw)
+
+
+@pytest.mark.parametrize("qs", [False, True])
+@pytest.mark.parametrize("BN", [(2, 321), (13, 875), (24, 290)])
+def test_f16_attention_exact(BN, qs):
+    """A forward whose every softmax term is a power of two: each form within one half ulp of the exactly known answer."""
+    with _lib.flavour("f16"):
+        AC.case_attention_exact(DEV, *BN, qs=qs)
+
+
+@pytest.mark.parametrize("BN", [(2, 321), (13, 875)])
+def test_f16_attention_exact_rescale_paths(BN):
+    """The exact forward with the levels that send the persistent kernel down pw_softmax_slow (test_kernels_gpu.py), in the half build."""
+    with _lib.flavour("f16"):
+        AC.case_attention_exact(DEV, *BN, hot=True)
 
 
 def test_f16_patch_embed():

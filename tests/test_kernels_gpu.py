@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import attention_cases as AC
 from tests import kernel_cases as KC
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +166,41 @@ def test_attention_backward_persistent_crosses_item_boundaries(BN):
     item's K / V / query tiles prefetched under the current one, dK / dV stored a step late); against the fp32 autograd
     oracle and bit for bit against the one-workgroup-per-item form."""
     KC.case_attention(DEV, torch.bfloat16, *BN)
+
+
+# one full tile; two tiles plus one row; the fused backward, ragged; the persistent fused backward crossing items (with the pre-scaled q contract
+# as well); the smallest persistent forward with the two-kernel backward; the eval shape; the persistent forward walking items; restricted rows
+CALIBRATED = [(1, 64, {}), (1, 129, {}), (3, 281, {}), (24, 290, {}), (24, 290, {"qs": True}), (2, 321, {}), (2, 560, {}), (13, 875, {}),
+              (3, 290, {"q_rows": 2})]
+
+
+@pytest.mark.parametrize("B,N,kw", CALIBRATED)
+def test_attention_calibrated(B, N, kw):
+    """Every bf16 forward form (four wave counts included) and backward form inside 1.25 x (rms) / 2 x (max) of the error its own bf16
+    roundings make, against fp64 softmax attention and its autograd (tests/attention_cases.py)."""
+    AC.case_attention_calibrated(DEV, B, N, **kw)
+
+
+@pytest.mark.parametrize("qs", [False, True])
+@pytest.mark.parametrize("BN", [(2, 321), (13, 875), (24, 290)])
+def test_attention_exact(BN, qs):
+    """A forward whose every softmax term is a power of two: each form within one bf16 ulp of the exactly known answer."""
+    AC.case_attention_exact(DEV, *BN, qs=qs)
+
+
+@pytest.mark.parametrize("BN", [(2, 321), (13, 875)])
+def test_attention_exact_rescale_paths(BN):
+    """The exact forward with the levels that send the persistent kernel down pw_softmax_slow: a first tile whose half-row sum is below
+    1e-30, a later tile (and, for some classes, the first) whose sum passes 4096."""
+    AC.case_attention_exact(DEV, *BN, hot=True)
+
+
+def test_bf16_conversions_round_like_torch():
+    """cast_weights(_multi), cast_rows and the bf16 GEMM output of each kernel (128 x 128, owned 256-row, eight-wave, 128-row tiles) bit for
+    bit against torch's .bfloat16(): ties to even, +-inf from the tie 3.3962e38, the subnormal range (bf16 subnormals through the MFMA
+    operand path and fp32 subnormals through the epilogue's acc + bias)."""
+    forms = ({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}, {"gemm_min_m": 512, "gemm_variant": 3}, {"gemm_min_m": 512, "gemm_tail": 2})
+    KC.case_half_conversions(DEV, M=1024, N=512, K=64, forms=forms)
 
 
 def test_split_bf16_products():
