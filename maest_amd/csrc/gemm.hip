@@ -23,6 +23,7 @@
 //     The bias gradient (column sum of A over the tokens) rides along as one extra MFMA against a
 //     fragment of ones in the tile_j == 0 workgroups.  Split-K partials are combined with fp32 atomics.
 #include "common.h"
+#include "gemm256_epi.h"     // mul16_chunk
 
 namespace maest {
 
@@ -138,6 +139,21 @@ __device__ __forceinline__ void epi_drain(const char* smem, void* dst, int64_t l
     }
 }
 
+// MUL with a 16-bit output: the tile staged in fp32 (EpiCfg<4>) times the 16-bit aux, rounded once (gemm256_epi.h: mul16_chunk)
+__device__ __forceinline__ void epi_drain_mul16(const char* smem, void* dst, int64_t ld, const void* aux, int64_t ld_aux,
+                                                int m0, int n0, int M, int N, int tid) {
+    using E = EpiCfg<2>;
+#pragma unroll 4
+    for (int c = tid; c < 128 * E::CPR; c += 256) {
+        const int row = c / E::CPR, cc = c - row * E::CPR;
+        const int gm = m0 + row, gn = n0 + cc * E::EPC;
+        if (gm >= M || gn >= N) continue;
+        const chunk16 r = *reinterpret_cast<const chunk16*>(reinterpret_cast<const bf16_t*>(aux) + (int64_t)gm * ld_aux + gn);
+        const chunk16 v = mul16_chunk(smem + row * EpiCfg<4>::PITCH + cc * 32, r);
+        __builtin_nontemporal_store(v, reinterpret_cast<chunk16*>(reinterpret_cast<char*>(dst) + ((int64_t)gm * ld + gn) * 2));
+    }
+}
+
 template <int OSZ, bool EXACT>
 __device__ __forceinline__ void epi_vector(char* smem, const f32x16_t (&acc)[2][2], const GemmParams& p, int m0, int n0,
                                            int wm, int wn, int lane, int tid) {
@@ -159,9 +175,16 @@ __device__ __forceinline__ void epi_vector(char* smem, const f32x16_t (&acc)[2][
             epi_drain<OSZ, 1>(smem, p.C, p.ldc, p.aux_in, p.ld_aux, m0, n0, p.M, p.N, tid);
             break;
         case MAEST_EPI_MUL:
-            epi_stage<OSZ, 0, EXACT>(smem, acc, p.bias, n0, p.N, wm, wn, lane);
-            __syncthreads();
-            epi_drain<OSZ, 2>(smem, p.C, p.ldc, p.aux_in, p.ld_aux, m0, n0, p.M, p.N, tid);
+            if constexpr (OSZ == 2) {
+                // one fp32 multiply of acc + bias and one rounding: the sums are staged in fp32, the drain multiplies and converts
+                epi_stage<4, 0, EXACT>(smem, acc, p.bias, n0, p.N, wm, wn, lane);
+                __syncthreads();
+                epi_drain_mul16(smem, p.C, p.ldc, p.aux_in, p.ld_aux, m0, n0, p.M, p.N, tid);
+            } else {
+                epi_stage<OSZ, 0, EXACT>(smem, acc, p.bias, n0, p.N, wm, wn, lane);
+                __syncthreads();
+                epi_drain<OSZ, 2>(smem, p.C, p.ldc, p.aux_in, p.ld_aux, m0, n0, p.M, p.N, tid);
+            }
             break;
         default:
             epi_stage<OSZ, 0, EXACT>(smem, acc, p.bias, n0, p.N, wm, wn, lane);

@@ -137,13 +137,19 @@ __device__ __forceinline__ void drain256(const char* smem, void* dst, int64_t ld
                                          int mbase, int n0, int M, int N, int tid, float* rowdot = nullptr, int ntok = 1,
                                          int row0 = 0) {
     using E = Epi256<OSZ>;
+    constexpr int SSZ = StageSz<OSZ, MODE>::value;          // MUL -> 16-bit: the tile is staged in fp32 (gemm256_epi.h: mul16_chunk)
 #pragma unroll
     for (int i = 0; i < ROWS * E::CPR / 512; ++i) {
         const int c = tid + i * 512;
         const int row = c / E::CPR, cc = c - row * E::CPR;
         const int gm = mbase + row, gn = n0 + cc * E::EPC;
-        chunk16 v = *reinterpret_cast<const chunk16*>(smem + row * E::PITCH + cc * 16);
-        if (MODE == 1 || MODE == 2) v = apply_aux<OSZ, MODE>(v, aux->v[i]);
+        chunk16 v;
+        if constexpr (SSZ != OSZ) {
+            v = mul16_chunk(smem + row * Epi256<SSZ>::PITCH + cc * 32, aux->v[i]);
+        } else {
+            v = *reinterpret_cast<const chunk16*>(smem + row * E::PITCH + cc * 16);
+            if (MODE == 1 || MODE == 2) v = apply_aux<OSZ, MODE>(v, aux->v[i]);
+        }
         if (MODE == 3) {
             const chunk16 r = aux->v[i];
             float d = 0.0f;
@@ -187,6 +193,24 @@ __device__ __forceinline__ void epilogue256(char* smem, const f32x16_t (&acc)[2]
         }
         return;
     }
+    if constexpr (OSZ == 2) {
+        if (p.epi == MAEST_EPI_MUL) {      // staged in fp32, 64 rows a pass (the fp32 output's geometry), converted by the drain: mul16_chunk
+            using F = Epi256<4>;
+#pragma unroll
+            for (int ps = 0; ps < F::PASSES; ++ps) {
+                const int pwm = ps / (4 / F::MT);
+                const int mt0 = (ps % (4 / F::MT)) * F::MT;
+                const int mbase = m0 + pwm * 128 + mt0 * 32;
+                AuxRegs<2, F::ROWS> ax;
+                ax.load(p.aux_in, p.ld_aux, mbase, n0, p.M, tid);
+                if (wm == pwm) stage256<4, 0, EXACT>(smem, acc, p.bias, n0, p.N, mt0, wn, lane);
+                __syncthreads();
+                drain256<2, 2, F::ROWS>(smem, p.C, p.ldc, &ax, mbase, n0, p.M, p.N, tid);
+                __syncthreads();
+            }
+            return;
+        }
+    }
     const bool with_aux = p.epi == MAEST_EPI_RESIDUAL || p.epi == MAEST_EPI_MUL || p.epi == MAEST_EPI_ROWDOT;   // block-uniform
 #pragma unroll
     for (int ps = 0; ps < E::PASSES; ++ps) {
@@ -226,10 +250,11 @@ __device__ __forceinline__ void epilogueT(char* smem, const f32x16_t (&acc)[2][4
     const bool gelu = p.epi == MAEST_EPI_GELU;
     const bool pair = gelu && p.aux_out != nullptr;
     // rows per pass so that the staging area (two regions for the pair form) fits the LDS ring it reuses
-    auto run = [&](auto rp_tag, auto pair_tag) {
+    auto run = [&](auto rp_tag, auto pair_tag, auto ssz_tag) {
         constexpr int RP = decltype(rp_tag)::value;
         constexpr bool PAIR = decltype(pair_tag)::value;
-        constexpr int REGION = RP * E::PITCH;
+        constexpr int SSZ = decltype(ssz_tag)::value;          // element size of the staging: OSZ, but fp32 for MUL -> 16-bit (gemm256_epi.h: mul16_chunk)
+        constexpr int REGION = RP * EpiT<SSZ, TNC>::PITCH;
 #pragma unroll
         for (int ps = 0; ps < 256 / RP; ++ps) {
 #pragma unroll
@@ -238,7 +263,7 @@ __device__ __forceinline__ void epilogueT(char* smem, const f32x16_t (&acc)[2][4
                 if (r0 >= ps * RP && r0 < (ps + 1) * RP) {
                     if (PAIR) stageT<OSZ, 3, EXACT, TNC>(smem, REGION, acc[0][mt], acc[1][mt], p.bias, n0, p.N, r0 - ps * RP, wn, lane);
                     else if (gelu) stageT<OSZ, 1, EXACT, TNC>(smem, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, r0 - ps * RP, wn, lane);
-                    else stageT<OSZ, 0, EXACT, TNC>(smem, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, r0 - ps * RP, wn, lane);
+                    else stageT<SSZ, 0, EXACT, TNC>(smem, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, r0 - ps * RP, wn, lane);
                 }
             }
             __syncthreads();
@@ -249,15 +274,18 @@ __device__ __forceinline__ void epilogueT(char* smem, const f32x16_t (&acc)[2][4
             } else if (p.epi == MAEST_EPI_RESIDUAL) {
                 drainT<OSZ, 1, TNC, NTH>(smem, RP, p.C, p.ldc, p.aux_in, p.ld_aux, mbase, n0, p.M, p.N, tid);
             } else if (p.epi == MAEST_EPI_MUL) {
-                drainT<OSZ, 2, TNC, NTH>(smem, RP, p.C, p.ldc, p.aux_in, p.ld_aux, mbase, n0, p.M, p.N, tid);
+                if constexpr (SSZ == StageSz<OSZ, 2>::value)
+                    drainT<OSZ, 2, TNC, NTH>(smem, RP, p.C, p.ldc, p.aux_in, p.ld_aux, mbase, n0, p.M, p.N, tid);
             } else {
                 drainT<OSZ, 0, TNC, NTH>(smem, RP, p.C, p.ldc, nullptr, 0, mbase, n0, p.M, p.N, tid);
             }
             if (ps + 1 < 256 / RP) __syncthreads();
         }
     };
-    if (pair) run(std::integral_constant<int, (OSZ == 2 ? 128 : 64)>{}, std::true_type{});
-    else run(std::integral_constant<int, (OSZ == 2 ? 256 : 128)>{}, std::false_type{});
+    using osz_t = std::integral_constant<int, OSZ>;
+    if (pair) run(std::integral_constant<int, (OSZ == 2 ? 128 : 64)>{}, std::true_type{}, osz_t{});
+    else if (OSZ == 2 && p.epi == MAEST_EPI_MUL) run(std::integral_constant<int, 128>{}, std::false_type{}, std::integral_constant<int, 4>{});
+    else run(std::integral_constant<int, (OSZ == 2 ? 256 : 128)>{}, std::false_type{}, osz_t{});
 }
 
 constexpr int W2_ROWB = 128;
@@ -274,7 +302,8 @@ constexpr int W2_SMEM = W2_NBUF * W2_UNIT;  // 163840
 template <int OSZ, bool EXACT, bool PAIR, int MODE>
 __device__ __forceinline__ void epilogueW_run(char* smem, const f32x16_t (&acc)[2][4], const Gemm256Params& p, int m0,
                                               int n0, int wm, int wn, int lane, int tid, bool gelu) {
-    using E = EpiT<OSZ, 256>;
+    constexpr int SSZ = StageSz<OSZ, MODE>::value;              // MUL -> 16-bit is staged in fp32 (gemm256_epi.h: mul16_chunk)
+    using E = EpiT<SSZ, 256>;
     constexpr int REGION = 64 * E::PITCH;                       // one 64-row staging region: 33792 / 66560
     constexpr int BUF = (PAIR ? 2 : 1) * REGION;
     constexpr bool DOUBLE = 2 * BUF <= W2_SMEM;                 // everything but the fp32 value + GELU' pair
@@ -284,7 +313,7 @@ __device__ __forceinline__ void epilogueW_run(char* smem, const f32x16_t (&acc)[
             if (mt == ps) {
                 if (PAIR) stageT<OSZ, 3, EXACT, 256>(buf, REGION, acc[0][mt], acc[1][mt], p.bias, n0, p.N, wm * 32, wn, lane);
                 else if (gelu) stageT<OSZ, 1, EXACT, 256>(buf, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, wm * 32, wn, lane);
-                else stageT<OSZ, 0, EXACT, 256>(buf, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, wm * 32, wn, lane);
+                else stageT<SSZ, 0, EXACT, 256>(buf, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, wm * 32, wn, lane);
             }
     };
     // aux_in of the RESIDUAL / MUL forms: fetched one pass ahead into registers (see AuxRegs)
@@ -349,7 +378,7 @@ __device__ __forceinline__ void epilogueW(char* smem, const f32x16_t (&acc)[2][4
 template <int OSZ, bool EXACT, int MODE, bool PAIR>
 __device__ __forceinline__ void epilogueH_run(char* smem, const f32x16_t (&acc)[2][2], const Gemm256Params& p, int m0,
                                               int n0, int wm, int wn, int lane, int tid, bool gelu) {
-    using E = EpiT<OSZ, 256>;
+    using E = EpiT<StageSz<OSZ, MODE>::value, 256>;             // MUL -> 16-bit is staged in fp32 (gemm256_epi.h: mul16_chunk)
     constexpr int PMT = (PAIR && OSZ == 4) ? 1 : 2;             // m-tiles per wave and pass
     constexpr int GR = 32 * PMT;                                // rows per wave group and pass
     constexpr int REGION = 2 * GR * E::PITCH;                   // value region; the GELU' region follows
@@ -366,7 +395,7 @@ __device__ __forceinline__ void epilogueH_run(char* smem, const f32x16_t (&acc)[
             const int lrow = wm * GR + mi * 32;
             if (PAIR) stageT<OSZ, 3, EXACT, 256>(smem, REGION, acc[0][mt], acc[1][mt], p.bias, n0, p.N, lrow, wn, lane);
             else if (gelu) stageT<OSZ, 1, EXACT, 256>(smem, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, lrow, wn, lane);
-            else stageT<OSZ, 0, EXACT, 256>(smem, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, lrow, wn, lane);
+            else stageT<StageSz<OSZ, MODE>::value, 0, EXACT, 256>(smem, 0, acc[0][mt], acc[1][mt], p.bias, n0, p.N, lrow, wn, lane);
         }
         __syncthreads();
 #pragma unroll

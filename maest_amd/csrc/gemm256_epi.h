@@ -63,6 +63,22 @@ __device__ __forceinline__ chunk16 apply_aux(chunk16 v, const chunk16& r) {
     return v;
 }
 
+// MUL with a 16-bit output: (acc + bias) * aux is ONE fp32 multiply and ONE rounding, so the sums are staged in fp32 (the OSZ = 4 layout of
+// the same staging code) and the drain converts: eight staged fp32 values at `src` times the eight 16-bit aux values `r` -> one 16-byte chunk
+// of 16-bit results (tests/epilogue_cases.py: case_epilogue_exact pins the single rounding).
+__device__ __forceinline__ chunk16 mul16_chunk(const char* src, const chunk16& r) {
+    const chunk16 v0 = *reinterpret_cast<const chunk16*>(src), v1 = *reinterpret_cast<const chunk16*>(src + 16);
+    chunk16 o;
+    o[0] = pack_bf2(u2f(v0[0]) * lo16f(r[0]), u2f(v0[1]) * hi16f(r[0]));
+    o[1] = pack_bf2(u2f(v0[2]) * lo16f(r[1]), u2f(v0[3]) * hi16f(r[1]));
+    o[2] = pack_bf2(u2f(v1[0]) * lo16f(r[2]), u2f(v1[1]) * hi16f(r[2]));
+    o[3] = pack_bf2(u2f(v1[2]) * lo16f(r[3]), u2f(v1[3]) * hi16f(r[3]));
+    return o;
+}
+// element size of the LDS staging of an epilogue form: the output's, but fp32 for MUL (MODE 2) with a 16-bit output
+template <int OSZ, int MODE>
+struct StageSz { static constexpr int value = (MODE == 2 && OSZ == 2) ? 4 : OSZ; };
+
 // ---- C-tile epilogue shared by the full-line 256x256 kernel (TNC = 256 columns, 512 threads, 160 KiB of LDS) and the
 // 256x128 kernel (TNC = 128, 256 threads, 72 KiB): the whole tile -- or the largest row group that fits, with two
 // regions for the GELU + GELU' pair -- is staged in ONE pass by ALL waves at once (the older epilogue256 staged one
@@ -118,13 +134,22 @@ template <int OSZ, int MODE, int TNC, int NTH>
 __device__ __forceinline__ void drainT(const char* smem, int rows, void* dst, int64_t ld, const void* aux,
                                        int64_t ld_aux, int mbase, int n0, int M, int N, int tid) {
     using E = EpiT<OSZ, TNC>;
+    constexpr int SSZ = StageSz<OSZ, MODE>::value;
+    using S = EpiT<SSZ, TNC>;                       // the staged tile's layout
 #pragma unroll 4
     for (int c = tid; c < rows * E::CPR; c += NTH) {
         const int row = c / E::CPR, cc = c - row * E::CPR;
         const int gm = mbase + row, gn = n0 + cc * E::EPC;
         if (gm >= M || gn >= N) continue;
-        chunk16 v = *reinterpret_cast<const chunk16*>(smem + row * E::PITCH + cc * 16);
-        if (MODE == 1) {
+        chunk16 v;
+        if constexpr (SSZ != OSZ) {
+            const chunk16 r = *reinterpret_cast<const chunk16*>(reinterpret_cast<const bf16_t*>(aux) + (int64_t)gm * ld_aux + gn);
+            v = mul16_chunk(smem + row * S::PITCH + cc * 32, r);
+        } else {
+            v = *reinterpret_cast<const chunk16*>(smem + row * E::PITCH + cc * 16);
+        }
+        if (SSZ != OSZ) {           // (multiplied and converted above)
+        } else if (MODE == 1) {
             const float4 r = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(aux) + (int64_t)gm * ld_aux + gn);
             v[0] = f2u(u2f(v[0]) + r.x); v[1] = f2u(u2f(v[1]) + r.y);
             v[2] = f2u(u2f(v[2]) + r.z); v[3] = f2u(u2f(v[3]) + r.w);

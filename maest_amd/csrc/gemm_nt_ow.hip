@@ -65,10 +65,14 @@ template <int OSZ, int GMODE, int MODE, typename NEXT>
 __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gemm256Params& p, int m0, int n0, int wm, int wn,
                                                 int lane, int tid, NEXT&& request_next) {
     using E = EpiT<OSZ, 256>;
+    // MUL with a 16-bit output: (acc + bias) * aux is one fp32 multiply and one rounding -- the sums are staged in fp32 (SSZ = 4: the fp32
+    // output's staging layout), the drain multiplies and converts (gemm256_epi.h: mul16_chunk)
+    constexpr int SSZ = StageSz<OSZ, MODE>::value;
+    using S = EpiT<SSZ, 256>;
     constexpr bool SPLIT = GMODE == 4;
     constexpr bool PAIR = GMODE == 3 || SPLIT;
     static_assert(!SPLIT || (OSZ == 2 && MODE == 0), "split rows: bf16 thirds, no second operand");
-    constexpr int REGION = 64 * E::PITCH;                       // one 64-row staging region: 33792 / 66560
+    constexpr int REGION = 64 * S::PITCH;                       // one 64-row staging region: 33792 / 66560
     constexpr int BUF = (PAIR ? 2 : 1) * REGION;
     constexpr int BIAS0 = OW_BIAS0;                             // 256 floats behind the (largest) staging buffer, stored by the caller
     static_assert(BUF <= OW_BIAS0 && OW_EPI0 + BIAS0 + 1024 <= OW_SMEM, "the staging buffer and the bias row");
@@ -92,8 +96,8 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
             v[e] = gv[0]; v[e + 1] = gv[1];
             d[e] = dv[0]; d[e + 1] = dv[1];
         }
-        char* dst = row + (N16 * 16) * OSZ;
-        if (OSZ == 4) {
+        char* dst = row + (N16 * 16) * SSZ;
+        if (SSZ == 4) {
             *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
             if (PAIR) *reinterpret_cast<float4*>(dst + REGION) = make_float4(d[0], d[1], d[2], d[3]);
         } else {
@@ -120,8 +124,8 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
     auto stage = [&](auto ps_tag, char* buf) {
         using std::integral_constant;
         constexpr int PS = decltype(ps_tag)::value;
-        char* row0 = buf + (wm * 32 + (lane & 15)) * E::PITCH + (wn * 128 + 4 * q16) * OSZ;
-        char* row1 = row0 + 16 * E::PITCH;
+        char* row0 = buf + (wm * 32 + (lane & 15)) * S::PITCH + (wn * 128 + 4 * q16) * SSZ;
+        char* row1 = row0 + 16 * S::PITCH;
         constexpr integral_constant<int, 2 * PS> M0{};
         constexpr integral_constant<int, 2 * PS + 1> M1{};
         f32x4_t b = bias_blk(0), bn = bias_blk(1);
@@ -147,7 +151,7 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
     const char* a_col = reinterpret_cast<const char*>(p.aux_in) + col;
     const char* a_thr = a_col + (int64_t)(m0 + r0) * x_row;
     char* o_thr = reinterpret_cast<char*>(p.aux_out) + (int64_t)(m0 + r0) * x_row + col;
-    const int l_thr = r0 * E::PITCH + cc * 16;
+    const int l_thr = r0 * S::PITCH + cc * (16 * SSZ / OSZ);
     chunk16 ax[2][NCH];                                         // [32-row group]: the RESIDUAL / MUL operand of the pass to drain
     auto prefetch = [&](int ps) {
 #pragma unroll
@@ -163,11 +167,14 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
     auto drain_one = [&](const char* src, char* dthr, int64_t drow, const chunk16* aux, int ro0) {
         chunk16 v[NCH];
 #pragma unroll
-        for (int i = 0; i < NCH; ++i) v[i] = *reinterpret_cast<const chunk16*>(src + l_thr + i * RS * E::PITCH);
+        for (int i = 0; i < NCH; ++i) {
+            if constexpr (SSZ != OSZ) v[i] = mul16_chunk(src + l_thr + i * RS * S::PITCH, aux[i]);
+            else v[i] = *reinterpret_cast<const chunk16*>(src + l_thr + i * RS * E::PITCH);
+        }
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
             chunk16 o = v[i];
-            if (aux != nullptr) o = apply_aux<OSZ, MODE>(o, aux[i]);
+            if (SSZ == OSZ && aux != nullptr) o = apply_aux<OSZ, MODE>(o, aux[i]);
             if constexpr (MODE == 3) {
                 // row-dot side output (gemm256.hip: drain256): the stored values times `other` over each 64-column group -- the
                 // 8 / 16 lanes that hold a group's chunks are neighbours
@@ -195,7 +202,7 @@ __device__ __forceinline__ void ow_epilogue_run(char* smem0, OwCtx& c, const Gem
     auto drain = [&](int ps, const char* buf) {
 #pragma unroll
         for (int half = 0; half < 2; ++half) {                  // the two 32-row groups of a pass are 128 rows apart
-            const char* src = buf + half * 32 * E::PITCH;
+            const char* src = buf + half * 32 * S::PITCH;
             drain_one(src, c_thr, c_row, MODE != 0 ? ax[half] : nullptr, half * 128 + ps * 32);
             if (SPLIT) {
                 drain_one(src, c_thr + (int64_t)p.N * 2, c_row, nullptr, half * 128 + ps * 32);

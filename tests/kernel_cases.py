@@ -9,6 +9,9 @@ The same cases run under the half-precision build (`with _lib.flavour("f16")`, l
 torch.bfloat16 is the 16-bit operand CONTAINER whose bits the kernels read as IEEE half.  Every 16-bit operand is made with lp()
 and read back with f32(), which follow the calling thread's build; 16-bit tolerances come from t16(bf16 value, f16 value).
 (A tensor tagged torch.float16 is something else: the loader's half mel input, MAEST_F16, in both builds.)
+
+16-bit results of the GEMM epilogues, LayerNorm and the patch-embed backward are also held to the rounding bracket close16(): the stored value
+must be the round-to-nearest-even rounding of an fp32 value within a derived delta of an fp64 reference.
 """
 import math
 
@@ -116,10 +119,115 @@ def tol(dtype):
     return (2e-5, 2e-5) if dtype == torch.float32 else (2e-2, 2e-2)
 
 
+def _neighbour16(t, up):
+    """The next value of the calling build's 16-bit format above (`up`) or below each element of the container `t`."""
+    bits = t.view(torch.int16).to(torch.int32) & 0xffff
+    mag = bits & 0x7fff
+    o = torch.where(bits >= 0x8000, -mag, mag) + (1 if up else -1)          # the format's values in order; -0 and +0 are one
+    return (o.abs() | torch.where(o < 0, 0x8000, 0)).to(torch.int16).view(torch.bfloat16)
+
+
+def _fail(what, bad, ratio, got, ref, delta):
+    """Raise for the elements `bad`, naming the worst one by `ratio` = err / delta (NaN results count as the worst)."""
+    worst = torch.where(bad, torch.nan_to_num(ratio, nan=float("inf"), posinf=float("inf")), torch.full_like(ratio, -1.0))
+    i = tuple(int(v) for v in np.unravel_index(int(worst.argmax()), tuple(ratio.shape)))
+    raise AssertionError(f"{what}: {int(bad.sum())}/{bad.numel()} elements outside the gate; worst err / delta {float(ratio[i]):.3f} at {i}: "
+                         f"got {float(got[i])!r}, reference {float(ref[i])!r}, delta {float(delta[i]):.3e}")
+
+
+def close16(got, ref64, delta, what):
+    """The rounding-bracket gate of a 16-bit result.  `got`: a 16-bit container of the calling build; `ref64`: the fp64 reference; `delta`
+    (fp64, broadcast against ref64): the bound on the error of the fp32 value the kernel holds BEFORE its store.  Holds where
+        lp((ref64 - delta).float()) <= f32(got) <= lp((ref64 + delta).float()),
+    i.e. where the stored value is the round-to-nearest-even 16-bit rounding of some fp32 value within delta of the truth (rounding is monotonic:
+    exact, no ulp arithmetic at binade edges).  Every element is gated; NaN fails.  Feeds record() like close().  Returns the worst err / delta,
+    err = the distance from ref64 to the nearest real number that rounds to `got` (<= 1 where the gate holds, ties aside)."""
+    got = got.detach().cpu()
+    assert got.dtype == torch.bfloat16, (what, got.dtype)
+    ref64 = ref64.detach().cpu().double()
+    delta = delta.detach().cpu().double().expand_as(ref64)
+    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    g = f32(got).double()
+    lo, hi = f32(lp((ref64 - delta).float())).double(), f32(lp((ref64 + delta).float())).double()
+    if _errs is not None:
+        _errs[what] = max(_errs.get(what, 0.0), float((g - ref64).abs().max()) / (float(ref64.abs().max()) + 1e-30))
+    # the reals that round to got: between the midpoints to its two neighbours
+    below, above = (g + f32(_neighbour16(got, False)).double()) / 2, (g + f32(_neighbour16(got, True)).double()) / 2
+    err = torch.maximum(torch.maximum(below - ref64, ref64 - above), torch.zeros_like(g))
+    ratio = torch.where(err > 0, err / delta.clamp_min(1e-300), torch.zeros_like(err))          # (NaN where got is NaN)
+    bad = ~((lo <= g) & (g <= hi))
+    if bool(bad.any()):
+        _fail(what, bad, ratio, g, ref64, delta)
+    return float(ratio.max())
+
+
+def close32(got, ref64, delta, what):
+    """close16's companion for an fp32 result: |got - ref64| <= delta + 2^-24 |ref64| (the error before the store, and the store's own rounding),
+    every element, NaN fails.  Returns the worst err / (delta + 2^-24 |ref64|)."""
+    got = got.detach().cpu()
+    assert got.dtype == torch.float32, (what, got.dtype)
+    ref64 = ref64.detach().cpu().double()
+    lim = delta.detach().cpu().double().expand_as(ref64) + 2.0 ** -24 * ref64.abs()
+    assert got.shape == ref64.shape, (what, got.shape, ref64.shape)
+    err = (got.double() - ref64).abs()
+    if _errs is not None:
+        _errs[what] = max(_errs.get(what, 0.0), float(err.max()) / (float(ref64.abs().max()) + 1e-30))
+    ratio = torch.where(err > 0, err / lim.clamp_min(1e-300), torch.zeros_like(err))
+    bad = ~(err <= lim)
+    if bool(bad.any()):
+        _fail(what, bad, ratio, got.double(), ref64, lim)
+    return float(ratio.max())
+
+
 # ------------------------------------------------------------------------------------------ GEMM
-def case_gemm(dev, dtype, M, N, K, seed=0, identity=True):
+def row_blocks(M, N, limit=1 << 22):
+    """Row slices of an [M, N] result of at most `limit` elements each: the fp64 references of the large shapes are made block by block."""
+    step = max(1, limit // N)
+    return [slice(r, min(M, r + step)) for r in range(0, M, step)]
+
+
+def gemm_ref64(a, b, bias):
+    """fp64 a b^T + bias on the (rounded) operands, and the accumulation term of DESIGN.md section 7b,
+        delta_acc = 2 (K + 1) 2^-24 (|a| |b|^T + |bias|):
+    at most one fp32 ulp of a partial sum per addition whichever way the matrix unit rounds -- twice Higham's bound of a K-term dot product."""
+    a64, b64 = f32(a).double(), f32(b).double()
+    ref = a64 @ b64.t()
+    mag = a64.abs() @ b64.abs().t()
+    if bias is not None:
+        ref, mag = ref + bias.double(), mag + bias.double().abs()
+    return ref, 2 * (a.shape[1] + 1) * 2.0 ** -24 * mag
+
+
+def gelu_fit_bound(dtype, M, N, K):
+    """The documented bound of the erf form behind maest_gemm_nt's GELU epilogue at this shape under the options in force (epilogue_cases.e_fit):
+    libm for fp32 operands, the four-term fit in the 256-row-tile kernels, Abramowitz-Stegun 7.1.26 in the 128 x 128 kernel."""
+    from tests import epilogue_cases as EC
+    if dtype == torch.float32:
+        return 0.0
+    big = M >= max(512, ops.get_option("gemm_min_m")) and N >= 256 and N % 256 == 0 and K % 64 == 0
+    return EC.E_FIT4 if big else EC.E_FIT5
+
+
+def gate_gelu(g, aux, a, b, bias, fit, what):
+    """GELU outputs of a GEMM on random operands under the rounding bracket: gelu within delta_acc * 1.13 + delta_g (1.13 = max |gelu'|), gelu'
+    within delta_acc * 0.80 + delta_dg (0.80 = max |gelu''| = 2 phi(0)); delta_g, delta_dg: epilogue_cases.deltas.  Every element, block by block."""
+    from tests import epilogue_cases as EC
+    worst = 0.0
+    for r in row_blocks(a.shape[0], b.shape[0]):
+        x, dacc = gemm_ref64(a[r], b, bias)
+        g64, dg64 = EC.gelu_ref(x)
+        dgl, ddl, _ = EC.deltas(x, g64, fit)
+        for got, ref, delta, name in ((g, g64, dacc * 1.13 + dgl, "gelu"), (aux, dg64, dacc * 0.80 + ddl, "gelu' (aux_out)")):
+            if got is not None:
+                gate = close16 if got.dtype == torch.bfloat16 else close32
+                worst = max(worst, gate(got[r], ref, delta, f"{what}: {name} under the rounding bracket"))
+    return worst
+
+
+def case_gemm(dev, dtype, M, N, K, seed=0, identity=True, wscale=1.0):
+    """wscale: the scale of the weights b (1 / sqrt(K): most GELU arguments inside |x| < 3, where the function bends)."""
     a = lp(rnd((M, K), seed), dtype)
-    b = lp(rnd((N, K), seed + 1), dtype)
+    b = lp(rnd((N, K), seed + 1, wscale), dtype)
     bias = rnd((N,), seed + 2)
     ref = f32(a) @ f32(b).t() + bias
     # fp32 accumulation-order noise of a K-term dot product of N(0,1) operands: ~ 4e-7 * K absolute
@@ -141,6 +249,7 @@ def case_gemm(dev, dtype, M, N, K, seed=0, identity=True):
     F.gelu(xr).sum().backward()
     close(aux, xr.grad, rt2, max(at2 * math.sqrt(K / 64), 2e-6), "gemm gelu aux (= gelu' saved for backward)")
     close(g, F.gelu(ref), rt2, at2 * math.sqrt(K / 64), "gemm gelu")
+    gate_gelu(g, aux, a, b, bias, gelu_fit_bound(dtype, M, N, K), "gemm")
     # residual epilogue
     res = rnd((M, N), seed + 3)
     c = ops.gemm_nt(a.to(dev), b.to(dev), bias.to(dev), out_dtype=torch.float32, epi=ops.EPI_RESIDUAL,
@@ -150,6 +259,10 @@ def case_gemm(dev, dtype, M, N, K, seed=0, identity=True):
     pre = lp(rnd((M, N), seed + 4), dtype)
     c = ops.gemm_nt(a.to(dev), b.to(dev), None, out_dtype=dtype, epi=ops.EPI_MUL, aux_in=pre.to(dev))
     close(c, (ref - bias) * f32(pre), rt2, at2 * math.sqrt(K / 64), "gemm mul")
+    for r in row_blocks(M, N):          # (acc * pre: one multiply, one rounding -- the accumulation term times |pre|)
+        x, dacc = gemm_ref64(a[r], b, None)
+        p64 = f32(pre[r]).double()
+        (close16 if dtype == torch.bfloat16 else close32)(c[r], x * p64, dacc * p64.abs(), "gemm mul under the rounding bracket")
     # split-K atomic accumulate
     acc = torch.zeros((M, N), dtype=torch.float32, device=dev)
     ops.gemm_nt(a.to(dev), b.to(dev), None, out=acc, epi=ops.EPI_ATOMIC, split_k=3)
@@ -211,6 +324,7 @@ def case_gemm_one_wave_per_simd(dev, M, N, K, seed=11, only=None, pair=True, bot
     _same_products(g_n, g_o, str(dev) == "cpu", "GELU of the pair form differs between the two 256 x 256 kernels", K)
     _same_products(aux_n, aux_o, str(dev) == "cpu", "GELU' of the pair form differs between the two 256 x 256 kernels", K)
     close(g_n, F.gelu(ref), t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3) * math.sqrt(K / 64), "one-wave-per-SIMD GEMM: gelu")
+    gate_gelu(g_n, aux_n, a.cpu(), w.cpu(), bias.cpu(), gelu_fit_bound(dt, M, N, K), "one-wave-per-SIMD GEMM")
 
 
 def case_gemm_rowdot(dev, dtype, M, N, K, ntok, seed=7):
@@ -225,6 +339,9 @@ def case_gemm_rowdot(dev, dtype, M, N, K, ntok, seed=7):
     ref = f32(a) @ f32(b).t() + bias
     rt, at = (1e-5, 4e-7 * K) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3) * math.sqrt(K / 64))
     close(c, ref, rt, at, "gemm rowdot: C")
+    for r in row_blocks(M, N):
+        ref64, dacc = gemm_ref64(a[r], b, bias)
+        (close16 if dtype == torch.bfloat16 else close32)(c[r], ref64, dacc, "gemm rowdot: C under the rounding bracket")
     assert rd.shape == (M // ntok, N // 64, ntok)
     want = (f32(c).cpu() * f32(other)).reshape(M // ntok, ntok, N // 64, 64).sum(-1).permute(0, 2, 1)
     close(rd, want, 1e-5, 1e-5 * math.sqrt(64) * float(f32(c).abs().max()), "gemm rowdot: per-(row, group) dot products")
@@ -320,6 +437,9 @@ def case_layernorm(dev, dtype, rows):
     ref = F.layer_norm(x, (768,), g, b, 1e-6)
     rt, at = (1e-5, 1e-5) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))
     close(y, ref, rt, at, "layernorm fwd")
+    if dtype == torch.bfloat16:         # the 16-bit rounding of a value the fp32 build's gate accepts
+        ref64 = F.layer_norm(x.double(), (768,), g.double(), b.double(), 1e-6)
+        close16(y, ref64, 1e-5 + 1e-5 * ref64.abs(), "layernorm fwd under the rounding bracket")
     close(mean, x.mean(1), 1e-5, 1e-6, "layernorm mean")
     close(rstd, 1.0 / torch.sqrt(x.var(1, unbiased=False) + 1e-6), 1e-5, 1e-6, "layernorm rstd")
     # residual add fused into the LayerNorm that follows it: x_new = x + delta exactly (one fp32 add per element),
@@ -354,6 +474,12 @@ def case_layernorm(dev, dtype, rows):
     dx, dx_lp = ops.layernorm_bwd(dy.to(dev), x.to(dev), g.to(dev), mean, rstd, dres.to(dev), dg, db, lp_dtype=dtype)
     close(dx, xr.grad + dres, 1e-4, 1e-5, "layernorm dx")
     close(dx_lp, xr.grad + dres, *((1e-4, 1e-5) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))), "layernorm dx_lp")
+    if dtype == torch.bfloat16:
+        x64 = x.double().requires_grad_(True)
+        F.layer_norm(x64, (768,), g.double(), b.double(), 1e-6).backward(f32(dy).double())
+        dx64 = x64.grad + dres.double()
+        close16(dx_lp, dx64, 1e-5 + 1e-4 * dx64.abs(), "layernorm dx_lp under the rounding bracket")
+        _bits_equal(dx_lp, dx.cpu(), "layernorm dx_lp = the 16-bit rounding of the dx of the same kernel")
     close(dg, gr.grad, 1e-4, 1e-4 * math.sqrt(rows), "layernorm dgamma")
     close(db, br.grad, 1e-4, 1e-4 * math.sqrt(rows), "layernorm dbeta")
     # compact residual gradient (the first 2 tokens of every clip of n_tok tokens; zero for the others): bit for bit
@@ -609,6 +735,8 @@ def case_patch_embed(dev, dtype, B, T, patchout=0, mix=False, seed=30, masked=Fa
     dp = ops.token_assemble_bwd(dx0.to(dev), B, Fp, Tt, toff, tok_dev, dtype, d_cls, d_dist, d_np, d_fp, d_tp)
     gk = convg.grad if keep is None else convg.grad[:, :, :, torch.from_numpy(keep).long()]
     close(dp, gk.permute(0, 2, 3, 1).reshape(B * Fp * Tk, 768), *((0, 1e-6) if dtype == torch.float32 else (t16(1e-2, 2.5e-3), t16(1e-2, 2.5e-3))), "dpatches")
+    if dtype == torch.bfloat16:
+        close16(dp, gk.permute(0, 2, 3, 1).reshape(B * Fp * Tk, 768).double(), torch.tensor(1e-6, dtype=torch.float64), "dpatches under the rounding bracket")
     close(d_cls, sdg["cls_token"].grad.reshape(768), 1e-5, 1e-5, "d cls")
     close(d_dist, sdg["dist_token"].grad.reshape(768), 1e-5, 1e-5, "d dist")
     close(d_np, sdg["new_pos_embed"].grad.reshape(2, 768), 1e-5, 1e-5, "d new_pos")

@@ -8,6 +8,7 @@ import torch
 
 from maest_amd import _lib, ops
 from tests import attention_cases as AC
+from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
 from tests.test_emu_grad_kernels import _case, _im2col_ref, _stripes
 
@@ -42,6 +43,15 @@ def test_emu_f16_gemm(emu16):
     """NT GEMM of the 128 x 128 kernel: NONE / GELU with aux / RESIDUAL / MUL / split-K, fp32 and 16-bit outputs, ragged N."""
     KC.controlled(KC.case_gemm, emu16, BF, 150, 200, 128)
     KC.controlled(KC.case_gemm, emu16, BF, 70, 51, 64)
+
+
+def test_emu_f16_gemm_gelu_arguments_where_the_function_bends(emu16, gemm_options):
+    """Weights scaled by 1 / sqrt(K): nearly every GELU argument inside |x| < 3 -- the 128 x 128 kernel, then the 256-row-tile kernels (against the
+    rounding brackets of kernel_cases.gate_gelu, eight times narrower in half: no control run)."""
+    with _lib.flavour("f16"):
+        KC.case_gemm(emu16, BF, 150, 200, 128, wscale=128 ** -0.5)
+        gemm_options(gemm_min_m=512)
+        KC.case_gemm(emu16, BF, 512, 256, 192, identity=False, wscale=192 ** -0.5)
 
 
 def test_emu_f16_gemm_256_tile_kernels(emu16, gemm_options):
@@ -153,6 +163,20 @@ def test_emu_f16_conversions_round_like_torch(emu16, gemm_options):
     torch's .half() bit for bit: round to nearest even, +-inf past 65504, subnormals kept."""
     with _lib.flavour("f16"):
         KC.case_half_conversions(emu16, M=512, N=256, K=64, forms=({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}))
+
+
+def test_emu_f16_gelu_on_the_exact_argument_grid(emu16):
+    """Every GELU output form of the half build (fp32, half, value + gelu' pair) on the exact-argument grid, inside the error the erf fit's
+    documented bound and the roundings allow (tests/epilogue_cases.py)."""
+    with _lib.flavour("f16"):
+        worst = EC.case_gelu_grid(emu16, BF, ({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}))
+    print("".join(f"\n  {k}: worst err / delta {v:.3f}" for k, v in worst.items()))
+
+
+def test_emu_f16_mul_and_residual_epilogues_are_exact(emu16):
+    """mul -> half: one fp32 multiply of acc + bias, one rounding; residual -> fp32: (acc + bias) + res -- bit for bit on exact accumulators."""
+    with _lib.flavour("f16"):
+        EC.case_epilogue_exact(emu16, BF, ({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}))
 
 
 def test_emu_f16_nonfinite_values_propagate(emu16):

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from tests import attention_cases as AC
+from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
 
 DT = [torch.float32, torch.bfloat16]
@@ -24,6 +25,14 @@ def test_emu_gemm(emu, dtype):
 def test_emu_gemm_ragged_n_scalar_epilogue(emu, dtype):
     K = 32 if dtype == torch.float32 else 64
     KC.case_gemm(emu, dtype, 70, 51, K)
+
+
+def test_emu_gemm_gelu_arguments_where_the_function_bends(emu, gemm_options):
+    """Weights scaled by 1 / sqrt(K): the GELU arguments have unit variance instead of std sqrt(K), so nearly all of them fall inside |x| < 3,
+    where the erf fit matters and a bf16 ulp is small -- the 128 x 128 kernel, then the 256-row-tile kernels."""
+    KC.case_gemm(emu, torch.bfloat16, 150, 200, 128, wscale=128 ** -0.5)
+    gemm_options(gemm_min_m=512)
+    KC.case_gemm(emu, torch.bfloat16, 512, 256, 384, identity=False, wscale=384 ** -0.5)
 
 
 @pytest.mark.parametrize("dtype", DT_BIG)
@@ -175,6 +184,25 @@ def test_emu_bf16_conversions_round_like_torch(emu, gemm_options):
     """cast_weights(_multi), cast_rows and a GEMM's bf16 output (the 128 x 128 kernel, and the one-wave-per-SIMD kernel's twin) against torch's
     .bfloat16() bit for bit: round to nearest even, +-inf past 3.3962e38, subnormals kept."""
     KC.case_half_conversions(emu, M=512, N=256, K=64, forms=({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}))
+
+
+# The kernel forms the emulator can afford for the exact-accumulator epilogue cases (tests/epilogue_cases.py): the 128 x 128 kernel and the
+# one-wave-per-SIMD kernel's twin with the eight-wave kernel behind it for the forms the twin does not serve; fp32 operands: the 128 x 128 kernel
+EMU_FORMS = ({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512})
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_emu_gelu_on_the_exact_argument_grid(emu, dtype):
+    """Every GELU output form (fp32, bf16, value + gelu' pair, split rows) on the 1/4096 grid over [-12, 12], +-0, +-16, +-100 and +- the largest
+    bf16: inside the error the erf fit's documented bound and the roundings allow."""
+    worst = EC.case_gelu_grid(emu, dtype, EMU_FORMS if dtype == torch.bfloat16 else EMU_FORMS[:1])
+    print("".join(f"\n  {k}: worst err / delta {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_emu_mul_and_residual_epilogues_are_exact(emu, dtype):
+    """mul -> bf16: one fp32 multiply of acc + bias, one rounding; residual -> fp32: (acc + bias) + res -- bit for bit on exact accumulators."""
+    EC.case_epilogue_exact(emu, dtype, EMU_FORMS if dtype == torch.bfloat16 else EMU_FORMS[:1])
 
 
 def test_emu_split_bf16_products(emu):

@@ -8,6 +8,7 @@ import torch
 
 from maest_amd import _lib
 from tests import attention_cases as AC
+from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
 
 pytestmark = pytest.mark.gpu
@@ -139,6 +140,28 @@ def test_f16_conversions_round_like_torch():
     forms = ({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}, {"gemm_min_m": 512, "gemm_variant": 3}, {"gemm_min_m": 512, "gemm_tail": 2})
     with _lib.flavour("f16"):
         KC.case_half_conversions(DEV, M=1024, N=512, K=64, forms=forms)
+
+
+def test_f16_gelu_on_the_exact_argument_grid():
+    """Every GELU output form (fp32, half, value + gelu' pair) of each kernel on exactly known arguments: inside the error the erf fit's
+    documented bound, v_exp / v_rcp and the roundings allow (tests/epilogue_cases.py)."""
+    with _lib.flavour("f16"):
+        worst = EC.case_gelu_grid(DEV, BF, EC.FORMS_ALL, M=1024, N=512, K=64)
+    print("".join(f"\n  {k}: worst err / delta {v:.3f}" for k, v in worst.items()))
+
+
+def test_f16_mul_and_residual_epilogues_are_exact():
+    """mul -> half: one fp32 multiply of acc + bias, one rounding; residual -> fp32: (acc + bias) + res -- bit for bit, each kernel."""
+    with _lib.flavour("f16"):
+        EC.case_epilogue_exact(DEV, BF, EC.FORMS_ALL, M=1024, N=512, K=64)
+
+
+def test_f16_gemm_gelu_arguments_where_the_function_bends(gemm_options):
+    """Weights scaled by 1 / sqrt(K): nearly every GELU argument inside |x| < 3."""
+    with _lib.flavour("f16"):
+        KC.case_gemm(DEV, BF, 1120, 2304, 768, wscale=768 ** -0.5)
+        gemm_options(gemm_min_m=512)
+        KC.case_gemm(DEV, BF, 777, 512, 192, wscale=192 ** -0.5)
 
 
 @pytest.mark.parametrize("flavour", ["f16", "bf16"])

@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from tests import attention_cases as AC
+from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
 
 pytestmark = pytest.mark.gpu
@@ -201,6 +202,28 @@ def test_bf16_conversions_round_like_torch():
     operand path and fp32 subnormals through the epilogue's acc + bias)."""
     forms = ({"gemm_min_m": 1 << 30}, {"gemm_min_m": 512}, {"gemm_min_m": 512, "gemm_variant": 3}, {"gemm_min_m": 512, "gemm_tail": 2})
     KC.case_half_conversions(DEV, M=1024, N=512, K=64, forms=forms)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_gelu_on_the_exact_argument_grid(dtype):
+    """Every GELU output form (fp32, bf16, value + gelu' pair, split rows) of each kernel (128 x 128, owned 256-row, eight-wave, 128-row tiles) on
+    exactly known arguments -- the 1/4096 grid over [-12, 12], +-0, +-16, +-100, +- the largest bf16 --: inside the error the erf fit's
+    documented bound, v_exp / v_rcp and the roundings allow (tests/epilogue_cases.py)."""
+    worst = EC.case_gelu_grid(DEV, dtype, EC.FORMS_ALL, M=1024, N=512, K=64)
+    print("".join(f"\n  {k}: worst err / delta {v:.3f}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_mul_and_residual_epilogues_are_exact(dtype):
+    """mul -> bf16: one fp32 multiply of acc + bias, one rounding; residual -> fp32: (acc + bias) + res -- bit for bit on exact accumulators, each kernel."""
+    EC.case_epilogue_exact(DEV, dtype, EC.FORMS_ALL, M=1024, N=512, K=64)
+
+
+def test_gemm_gelu_arguments_where_the_function_bends(gemm_options):
+    """Weights scaled by 1 / sqrt(K): nearly every GELU argument inside |x| < 3 (N(0, 1) weights: 8 % of them at K = 768)."""
+    KC.case_gemm(DEV, torch.bfloat16, 1120, 2304, 768, wscale=768 ** -0.5)
+    gemm_options(gemm_min_m=512)
+    KC.case_gemm(DEV, torch.bfloat16, 777, 512, 192, wscale=192 ** -0.5)
 
 
 def test_split_bf16_products():
