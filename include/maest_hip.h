@@ -127,7 +127,10 @@ int maest_kernel_forms(int* mask);
                                       attention forward chosen by shape; 4 / 5 / 6 / 8 force one (tests, A/B) */
 #define MAEST_OPT_TN_REDUCE 8 /* env MAEST_TN_REDUCE, default 0: split-K partials of the wgrad GEMM are combined with fp32 atomics; 1:
                                  maest_gemm_tn_ws uses the workspace it is given (partial tiles stored plainly, summed in split
-                                 order by a second kernel: bit-reproducible dW; no measurable cost on the training step) */
+                                 order by a second kernel: dW repeats bit for bit at the shapes the 256-tile kernels take; no
+                                 measurable cost on the training step).  NOT a reproducible wgrad by itself: colsum (the bias
+                                 gradient) keeps its atomics under this switch, and so do C and colsum at the shapes gemm_tn_kernel
+                                 serves (ragged M / N, few output tiles).  MAEST_OPT_DETERMINISTIC orders all of them. */
 #define MAEST_OPT_GEMM_WGS 9 /* env MAEST_GEMM_WGS, default 0: the bf16 NT GEMM (gemm_nt_ow.hip) launches one workgroup per tile; n > 0:
                                at most n workgroups, workgroup b walking tiles b, b + n, ... with the next tile's first operand units
                                requested from inside the epilogue (256 = one per CU; small values make a workgroup walk several tiles
@@ -137,6 +140,36 @@ int maest_kernel_forms(int* mask);
                                   at K = 768 in panels of 6, N = 2304 in 5 + 4); n > 0: panels of n tiles.  Results do not depend on it.
                                   Measured (profiles/r06_gemm_panels.txt): fabric reads of fc1 5.8 -> 4.0 x the operand bytes, time equal
                                   (they are Infinity-Cache hits), inference step +0.4 % -- hence off by default. */
+#define MAEST_OPT_DETERMINISTIC 11 /* env MAEST_DETERMINISTIC, default 0.  1: every entry point that sums gradients with fp32 atomics in an order
+                                     that varies from run to run takes an ORDERED form instead, so that -- for a fixed build, device type,
+                                     shapes and option values -- its results repeat bit for bit.  The default (0) launches exactly what it
+                                     launched before the switch existed.  With 1:
+                                     * maest_gemm_tn_ws: the split-K partials of C AND of colsum go through the caller's workspace and are
+                                       summed by a second kernel in this order, per element:  s = 0;  s += partial[split] for split = 0, 1,
+                                       ... (ascending K ranges; for colsum the j-tiles of a split in ascending order inside it);  dest =
+                                       dest + s -- the destination LAST (the order tn256_reduce_kernel always had for C).  All three TN
+                                       kernels have the form: the one-wave-per-SIMD bf16 kernel (its accumulators leave as they sit in
+                                       a0 .. a255), the eight-wave kernel, and the 128 x 128 kernel that serves ragged M / N and shapes of
+                                       few tiles (partials [split][M pad 128][N pad 128]).  maest_gemm_tn_workspace_bytes reports the
+                                       size: C partials plus colsum partials; non-zero for every shape with more than one split.  The
+                                       alignment conditions are those of MAEST_OPT_TN_REDUCE (workspace, C 16-byte aligned, ldc % 4 == 0).
+                                       maest_gemm_tn (no workspace), a workspace that is too small or misaligned, or a 256-tile plan of a
+                                       single split: the 128 x 128 kernel with ONE split -- one writer and one add per element of C and of
+                                       colsum: reproducible, and slow at large K (a training loop passes the workspace).
+                                     * maest_layernorm_bwd(_headres): the workgroups' dgamma / dbeta partials are parked in the first
+                                       2 x workgroups rows of dx_out, a second kernel sums them in workgroup order (16 ascending runs of
+                                       workgroups, then the runs in ascending order) and adds the sum to dgamma / dbeta last, a third
+                                       computes the parked rows of dx_out / dx_lp.  dres must not alias dx_out.  dx_out = NULL with more
+                                       than four rows: one workgroup (one add per column).  The order depends on rows and on
+                                       MAEST_OPT_LN_BWD_BLOCKS only.
+                                     * maest_head_pool_bwd: one workgroup; one add per column.
+                                     * maest_token_assemble_bwd: dpatches as before; every element of d_cls, d_dist, d_new_pos, d_freq_pos
+                                       and d_time_pos is summed by one thread over its tokens in ascending order, the clips in ascending
+                                       order inside a token, and added once.
+                                     * maest_colsum: one thread per column walks the rows in ascending order (chunks of 512 rows summed from 0, the chunk
+                                       sums added in ascending order, the destination last).
+                                     * maest_gemm_nt with split_k > 1 (MAEST_EPI_ATOMIC): MAEST_ERR_INVALID -- its combine has no ordered form.
+                                     Scope: one process, one GPU; across builds, shapes or option values (the split counts) sums differ. */
 #define MAEST_OPT_LN_BWD_BLOCKS 4 /* env MAEST_LN_BWD_BLOCKS, default 1024: workgroup cap of the LayerNorm backward grid */
 int maest_set_option(int opt, int value, int restore_default);
 int maest_get_option(int opt, int* value);
@@ -175,11 +208,12 @@ int maest_gemm_nt_rowdot(const void* A, int64_t lda, const void* B, int64_t ldb,
  *   colsum[m] (fp32, ACCUMULATED, may be NULL) += sum_k A[k,m]              (= the bias gradient)
  * dW = dY^T X of nn.Linear backward with A = dY [tokens, out], B = X [tokens, in].  Any K (the token
  * tail is zero-filled in LDS); rows of A / B must be 16-byte multiples (lda / ldb) and may be wider
- * than M / N.  split_k partials are combined with fp32 atomics; split_k = 0 picks it automatically. */
+ * than M / N.  split_k partials are combined with fp32 atomics (MAEST_OPT_DETERMINISTIC: see there); split_k = 0 picks it
+ * automatically. */
 int maest_gemm_tn(const void* A, int64_t lda, const void* B, int64_t ldb, int dtype, float* C,
                   int64_t ldc, int M, int N, int K, float* colsum, int split_k, void* stream);
-/* The same with a caller-owned scratch buffer (ABI 5): the DETERMINISTIC form of the split-K combine, selected by
- * MAEST_OPT_TN_REDUCE = 1.  Given `workspace_bytes` >= the figure maest_gemm_tn_workspace_bytes reports, of 16-byte aligned device
+/* The same with a caller-owned scratch buffer (ABI 5): the workspace form of the split-K combine of C, selected by
+ * MAEST_OPT_TN_REDUCE = 1 (and, with the column sums ordered as well and at every shape, by MAEST_OPT_DETERMINISTIC = 1).  Given `workspace_bytes` >= the figure maest_gemm_tn_workspace_bytes reports, of 16-byte aligned device
  * memory (and C 16-byte aligned, ldc % 4 == 0), the K-split partial tiles are written to it with plain 16-byte stores and a second
  * kernel adds them to C in split order: no atomics on C, so dW is bit-reproducible from run to run (colsum still uses atomics).
  * Measured against the atomics (profiles/r03_ab_tn_workspace_combine.txt): the GEMM + reduce pair timed alone is 21 % faster at the

@@ -112,7 +112,7 @@ FORM_GEMM_NT_OW, FORM_GEMM_TN_OW, FORM_ATTN_FWD_PW = 1, 2, 4
 
 ABI_VERSION = 9
 OPTIONS = {"gemm_min_m": 0, "gemm_variant": 1, "gemm_epilogue": 2, "attn_bwd": 3, "ln_bwd_blocks": 4, "gemm_tail": 5, "attn_fwd": 6, "attn_fwd_waves": 7,
-           "tn_reduce": 8, "gemm_wgs": 9, "gemm_panel": 10}
+           "tn_reduce": 8, "gemm_wgs": 9, "gemm_panel": 10, "deterministic": 11}
 
 _lib = None
 _lib_f16 = None

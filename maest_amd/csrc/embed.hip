@@ -158,7 +158,9 @@ __global__ __launch_bounds__(192) void token_assemble_kernel(const float* __rest
 // loads of four clips in flight, and adds its partial sums to the (pre-zeroed) parameter gradients with atomics -- the
 // time / frequency tables are reduced over tokens that way in any case.  (One workgroup per token walking all 256 clips
 // with 4-byte loads was latency-bound: 222 us for 341 MB; two slices with 16-byte accesses: 154 us.)
+// TABLES = false (MAEST_OPT_DETERMINISTIC): dpatches only; the parameter gradients come from token_tables_ordered_kernel.
 constexpr int TAB_SLICES = 2;      // swept 1..32 at B = 256: 189 / 154 / 177 / 282 / 483 / 912 us -- the atomics of every extra slice cost 28 us
+template <bool TABLES>
 __global__ __launch_bounds__(192) void token_assemble_bwd_kernel(const float* __restrict__ dx0, int B, int Fg, int P,
                                                                  int Tt, int toffset,
                                                                  const int32_t* __restrict__ tok_ft,
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(192) void token_assemble_bwd_kernel(const float* __
                                                                  float* __restrict__ d_freq_pos,
                                                                  float* __restrict__ d_time_pos) {
     const int Ntok = 2 + P;
-    const int n = blockIdx.x;
+    const int n = TABLES ? blockIdx.x : blockIdx.x + 2;
     const int c = threadIdx.x * 4;
     const int per = (B + (int)gridDim.y - 1) / (int)gridDim.y;
     const int b0 = blockIdx.y * per;
@@ -199,7 +201,7 @@ __global__ __launch_bounds__(192) void token_assemble_bwd_kernel(const float* __
         for (int u = 0; u < 4; ++u) one(b + u, g[u]);
     }
     for (; b < b1; ++b) one(b, *reinterpret_cast<const float4*>(src + b * bstride));
-    if (b0 >= b1) return;
+    if (!TABLES || b0 >= b1) return;
     if (n == 0) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) { unsafeAtomicAdd(d_cls + c + e, s[e]); unsafeAtomicAdd(d_new_pos + c + e, s[e]); }
@@ -215,6 +217,67 @@ __global__ __launch_bounds__(192) void token_assemble_bwd_kernel(const float* __
             unsafeAtomicAdd(d_freq_pos + (int64_t)(c + e) * Fg + f, s[e]);
             unsafeAtomicAdd(d_time_pos + (int64_t)(c + e) * Tt + tcol, s[e]);
         }
+    }
+}
+
+// The ordered form of the parameter gradients above (MAEST_OPT_DETERMINISTIC): destination d = blockIdx.x is cls (0), dist (1), frequency
+// row f = d - 2, or time column d - 2 - Fg of the table (the column toffset + t of a token is matched); blockIdx.y picks 256 of the 768
+// channels, a lane four of them (16-byte loads, 1 KiB per wave and row).  ONE thread sums a destination element: over its tokens in
+// ascending sequence order, over the clips in ascending order inside a token (sixteen clips' loads in flight, added in order), and adds the
+// sum to the (accumulated) gradient once.  No scratch; dx0 is read once more per table.
+__global__ __launch_bounds__(64) void token_tables_ordered_kernel(const float* __restrict__ dx0, int B, int Fg, int P, int Tt, int toffset,
+                                                                  const int32_t* __restrict__ tok_ft, float* __restrict__ d_cls,
+                                                                  float* __restrict__ d_dist, float* __restrict__ d_new_pos,
+                                                                  float* __restrict__ d_freq_pos, float* __restrict__ d_time_pos) {
+    const int Ntok = 2 + P;
+    const int d = blockIdx.x;
+    const int c = blockIdx.y * 256 + threadIdx.x * 4;
+    const int64_t bstride = (int64_t)Ntok * PE_D;
+    float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    auto token = [&](int n) {
+        const float* src = dx0 + (int64_t)n * PE_D + c;
+        int b = 0;
+        for (; b + 16 <= B; b += 16) {        // (72 destinations x 3 waves are all the parallelism there is: 16 KiB in flight per wave)
+            float4 g[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) g[u] = *reinterpret_cast<const float4*>(src + (b + u) * bstride);
+#pragma unroll
+            for (int u = 0; u < 16; ++u) { s[0] += g[u].x; s[1] += g[u].y; s[2] += g[u].z; s[3] += g[u].w; }
+        }
+        for (; b + 4 <= B; b += 4) {
+            float4 g[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) g[u] = *reinterpret_cast<const float4*>(src + (b + u) * bstride);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { s[0] += g[u].x; s[1] += g[u].y; s[2] += g[u].z; s[3] += g[u].w; }
+        }
+        for (; b < B; ++b) {
+            const float4 g = *reinterpret_cast<const float4*>(src + b * bstride);
+            s[0] += g.x; s[1] += g.y; s[2] += g.z; s[3] += g.w;
+        }
+    };
+    if (d < 2) {
+        token(d);
+        float* dtok = d == 0 ? d_cls : d_dist;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            dtok[c + e] = dtok[c + e] + s[e];
+            d_new_pos[d * PE_D + c + e] = d_new_pos[d * PE_D + c + e] + s[e];
+        }
+        return;
+    }
+    const bool is_f = d < 2 + Fg;
+    const int want = is_f ? d - 2 : d - 2 - Fg;           // frequency row / time column of the table
+    for (int j = 0; j < P; ++j) {                         // (wave-uniform)
+        const int key = is_f ? tok_ft[2 * j] : toffset + tok_ft[2 * j + 1];
+        if (key == want) token(2 + j);
+    }
+    float* tab = is_f ? d_freq_pos : d_time_pos;
+    const int ld = is_f ? Fg : Tt;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float* dst = tab + (int64_t)(c + e) * ld + want;
+        *dst = *dst + s[e];
     }
 }
 
@@ -462,7 +525,17 @@ extern "C" int maest_token_assemble_bwd(const float* dx0, int B, int P, int Fg, 
                   "maest_token_assemble_bwd: null pointer");
     MAEST_REQUIRE(B > 0 && P > 0 && Fg > 0 && Tt > 0, "maest_token_assemble_bwd: bad shape");
     static_assert(PE_D == 192 * 4, "token_assemble_bwd_kernel: one thread per four channels");
-    hipLaunchKernelGGL(token_assemble_bwd_kernel, dim3(2 + P, TAB_SLICES), dim3(192), 0, (hipStream_t)stream,
+    if (option(MAEST_OPT_DETERMINISTIC) != 0) {
+        // ordered parameter gradients (include/maest_hip.h: MAEST_OPT_DETERMINISTIC): dpatches by the same kernel without its atomics
+        if (dpatches != nullptr)
+            hipLaunchKernelGGL(token_assemble_bwd_kernel<false>, dim3(P, TAB_SLICES), dim3(192), 0, (hipStream_t)stream, dx0, B, Fg, P, Tt,
+                               toffset, tok_ft, dpatches, dtype, d_cls, d_dist, d_new_pos, d_freq_pos, d_time_pos);
+        static_assert(PE_D == 3 * 256, "token_tables_ordered_kernel: three channel groups of 64 lanes x 4");
+        hipLaunchKernelGGL(token_tables_ordered_kernel, dim3(2 + Fg + Tt, 3), dim3(64), 0, (hipStream_t)stream, dx0, B, Fg, P, Tt, toffset,
+                           tok_ft, d_cls, d_dist, d_new_pos, d_freq_pos, d_time_pos);
+        return check_launch("maest_token_assemble_bwd(ordered)");
+    }
+    hipLaunchKernelGGL(token_assemble_bwd_kernel<true>, dim3(2 + P, TAB_SLICES), dim3(192), 0, (hipStream_t)stream,
                        dx0, B, Fg, P, Tt, toffset, tok_ft, dpatches, dtype, d_cls, d_dist, d_new_pos, d_freq_pos,
                        d_time_pos);
     return check_launch("maest_token_assemble_bwd");

@@ -49,6 +49,8 @@ struct GemmParams {
     int vec_ok;      // NT: 16-byte staged epilogue allowed (alignment / divisibility checked on the host)
     int tiles_m, tiles_n;
     int k_slices_per_split;  // K slices handled by one blockIdx.y
+    float* ws;               // TN, ordered combine (MAEST_OPT_DETERMINISTIC): [split][tiles_m * 128][tiles_n * 128] partials of C, then
+                             // [split][tiles_m * 128] partials of colsum
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -422,7 +424,9 @@ __device__ __forceinline__ chunk16 ones_chunk<float>() {
     return c;
 }
 
-template <typename T>
+// WS: the split-K partials of C and of colsum are stored plainly into p.ws (one writer per element and split) and combined in ascending
+// split order by tn_small_reduce_kernel -- the ordered form of MAEST_OPT_DETERMINISTIC; the main loop is the same.
+template <typename T, bool WS = false>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmParams p) {
     using C = TnCfg<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -520,6 +524,33 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmParams p) {
         __syncthreads();
     }
 
+    if constexpr (WS) {
+        const int64_t mpad = (int64_t)p.tiles_m * 128, npad = (int64_t)p.tiles_n * 128;
+        float* wp = p.ws + (int64_t)blockIdx.y * mpad * npad;
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = j0 + wn * 64 + b * 32 + (lane & 31);
+            if (col >= p.N) continue;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = i0 + wm * 64 + a * 32 + frag_row(r, lane);
+                    if (row < p.M) wp[(int64_t)row * npad + col] = acc[a][b][r];
+                }
+        }
+        if (do_colsum && (lane & 31) == 0) {
+            float* cp = p.ws + (int64_t)gridDim.y * mpad * npad + (int64_t)blockIdx.y * mpad;
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = i0 + wm * 64 + a * 32 + frag_row(r, lane);
+                    if (row < p.M) cp[row] = acc_cs[a][r];
+                }
+        }
+        return;
+    }
     float* Cp = reinterpret_cast<float*>(p.C);
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
@@ -542,6 +573,41 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmParams p) {
                 if (row < p.M) unsafeAtomicAdd(p.colsum + row, acc_cs[a][r]);
             }
     }
+}
+
+// C[row][col] += sum over the splits, ascending, of the partials gemm_tn_kernel<T, true> left in the workspace (the sum starts from 0 and
+// is added to the destination last); threads past M * N do the same for colsum.  One writer per destination.
+__global__ __launch_bounds__(256) void tn_small_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C, int64_t ldc, int M, int N,
+                                                              int64_t mpad, int64_t npad, int splits, float* __restrict__ colsum) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t mn = (int64_t)M * N;
+    const float* src;
+    float* dst;
+    int64_t step;
+    if (idx < mn) {
+        const int64_t row = idx / N, col = idx - row * N;
+        src = ws + row * npad + col;
+        step = mpad * npad;
+        dst = C + row * ldc + col;
+    } else if (colsum != nullptr && idx < mn + M) {
+        src = ws + (int64_t)splits * mpad * npad + (idx - mn);
+        step = mpad;
+        dst = colsum + (idx - mn);
+    } else {
+        return;
+    }
+    float s = 0.0f;
+    int sp = 0;
+    for (; sp + 4 <= splits; sp += 4) {          // four loads in flight, added in split order
+        const float v0 = src[0], v1 = src[step], v2 = src[2 * step], v3 = src[3 * step];
+        s += v0; s += v1; s += v2; s += v3;
+        src += 4 * step;
+    }
+    for (; sp < splits; ++sp) {
+        s += src[0];
+        src += step;
+    }
+    *dst = *dst + s;
 }
 
 int gemm_nt256_try(const void* A, int64_t lda, const void* B, int64_t ldb, int in_dtype, void* C, int64_t ldc,
@@ -595,6 +661,37 @@ static int launch_gemm_tn(GemmParams& p, int split_k, hipStream_t stream) {
     hipLaunchKernelGGL(gemm_tn_kernel<T>, grid, dim3(256), TnCfg<T>::SMEM, stream, p);
     return check_launch("maest_gemm_tn");
 }
+// the ordered form: partials into p.ws, then the reduce kernel
+template <typename T>
+static int launch_gemm_tn_ws(GemmParams& p, int split_k, hipStream_t stream) {
+    static DeviceOnce once;
+    ensure_dynamic_lds(once, &gemm_tn_kernel<T, true>, TnCfg<T>::SMEM);
+    dim3 grid(p.tiles_m * p.tiles_n, split_k, 1);
+    hipLaunchKernelGGL((gemm_tn_kernel<T, true>), grid, dim3(256), TnCfg<T>::SMEM, stream, p);
+    const int rc = check_launch("maest_gemm_tn(ordered)");
+    if (rc != MAEST_OK) return rc;
+    const int64_t n = (int64_t)p.M * p.N + (p.colsum != nullptr ? p.M : 0);
+    hipLaunchKernelGGL(tn_small_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float*)p.ws,
+                       reinterpret_cast<float*>(p.C), p.ldc, p.M, p.N, (int64_t)p.tiles_m * 128, (int64_t)p.tiles_n * 128, split_k, p.colsum);
+    return check_launch("maest_gemm_tn(ordered, reduce)");
+}
+
+// split count and slices per split of gemm_tn_kernel for a shape (split_k = 0: automatic)
+static void tn_small_plan(int dtype, int M, int N, int K, int split_k, int* splits, int* per_split) {
+    if (split_k == 0) {
+        const int t = ((M + 127) / 128) * ((N + 127) / 128);
+        split_k = 1024 / t > 0 ? 1024 / t : 1;
+    }
+    const int ks = 128 / (dtype == MAEST_BF16 ? 2 : 4);
+    const int total = (K + ks - 1) / ks;
+    if (split_k > total) split_k = total;
+    *per_split = (total + split_k - 1) / split_k;
+    *splits = (total + *per_split - 1) / *per_split;
+}
+static int64_t tn_small_workspace_bytes(int M, int N, int splits) {
+    const int64_t mpad = (int64_t)((M + 127) / 128) * 128, npad = (int64_t)((N + 127) / 128) * 128;
+    return (int64_t)splits * (mpad * npad + mpad) * (int64_t)sizeof(float);
+}
 
 }  // namespace maest
 
@@ -626,11 +723,14 @@ extern "C" int maest_gemm_nt(const void* A, int64_t lda, const void* B, int64_t 
     MAEST_REQUIRE(split_k >= 1, "maest_gemm_nt: split_k must be >= 1");
     MAEST_REQUIRE(split_k == 1 || epi == MAEST_EPI_ATOMIC, "maest_gemm_nt: split_k > 1 needs MAEST_EPI_ATOMIC");
     MAEST_REQUIRE(epi != MAEST_EPI_ATOMIC || out_dtype == MAEST_F32, "maest_gemm_nt: atomic epilogue accumulates fp32");
+    MAEST_REQUIRE(split_k == 1 || option(MAEST_OPT_DETERMINISTIC) == 0,
+                  "maest_gemm_nt: split_k > 1 combines its partials with atomics in an order that varies from run to run: not available under "
+                  "MAEST_OPT_DETERMINISTIC (use split_k = 1)");
     MAEST_REQUIRE(epi != MAEST_EPI_RESIDUAL || (aux_in && out_dtype == MAEST_F32), "maest_gemm_nt: residual epilogue needs fp32 aux_in and fp32 out");
     MAEST_REQUIRE(epi != MAEST_EPI_MUL || aux_in, "maest_gemm_nt: mul epilogue needs aux_in");
     GemmParams p;
     p.A = (const char*)A; p.B = (const char*)B; p.C = C;
-    p.bias = bias; p.aux_in = aux_in; p.aux_out = aux_out; p.colsum = nullptr;
+    p.bias = bias; p.aux_in = aux_in; p.aux_out = aux_out; p.colsum = nullptr; p.ws = nullptr;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ld_aux = ld_aux;
     p.M = M; p.N = N; p.K = K;
     p.out_dtype = out_dtype; p.epi = epi;
@@ -701,6 +801,13 @@ extern "C" int maest_gemm_tn_workspace_bytes(int dtype, int M, int N, int K, int
     MAEST_REQUIRE(M > 0 && N > 0 && K > 0 && split_k >= 0, "maest_gemm_tn_workspace_bytes: bad shape M=%d N=%d K=%d", M, N, K);
     MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16 || dtype == MAEST_F32X3, "maest_gemm_tn_workspace_bytes: bad dtype %d", dtype);
     *bytes = gemm_tn256_workspace_bytes(dtype, M, N, K, split_k);
+    if (option(MAEST_OPT_DETERMINISTIC) != 0 && *bytes == 0) {
+        // shapes (and single-split plans) the 256-tile kernels leave to gemm_tn_kernel: its own ordered form
+        const int plain = dtype == MAEST_F32X3 ? MAEST_F32 : dtype;
+        int splits = 1, per = 0;
+        tn_small_plan(plain, M, N, K, split_k, &splits, &per);
+        if (splits >= 2) *bytes = tn_small_workspace_bytes(M, N, splits);
+    }
     return MAEST_OK;
 }
 
@@ -723,10 +830,34 @@ extern "C" int maest_gemm_tn_ws(const void* A, int64_t lda, const void* B, int64
     MAEST_REQUIRE((lda * elt) % 16 == 0 && (ldb * elt) % 16 == 0, "maest_gemm_tn: lda/ldb rows must be 16-byte multiples");
     MAEST_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "maest_gemm_tn: A/B must be 16-byte aligned");
     MAEST_REQUIRE(split_k >= 0, "maest_gemm_tn: split_k must be >= 0 (0 = automatic)");
+    const bool ordered = option(MAEST_OPT_DETERMINISTIC) != 0;
     {   // large aligned problems go to the 256x256 LDS-DMA kernel
         const int rc = gemm_tn256_try(A, lda, B, ldb, x3 ? MAEST_F32X3 : dtype, C, ldc, M, N, K, colsum, split_k,
                                       (hipStream_t)stream, workspace, workspace_bytes);
         if (rc >= 0) return rc;
+    }
+    if (ordered) {
+        // MAEST_OPT_DETERMINISTIC, shapes the 256-tile kernels did not take in their ordered form: this kernel's workspace form, or --
+        // no workspace, one too small, misaligned -- ONE split: every element of C and of colsum then has one writer and gets one add
+        int splits = 1, per = 0;
+        tn_small_plan(dtype, M, N, K, split_k, &splits, &per);
+        const bool use_ws = splits >= 2 && workspace != nullptr && workspace_bytes >= tn_small_workspace_bytes(M, N, splits) &&
+                            ((uintptr_t)workspace % 16) == 0 && ((uintptr_t)C % 16) == 0 && (ldc % 4) == 0;
+        if (!use_ws) tn_small_plan(dtype, M, N, K, 1, &splits, &per);
+        GemmParams p;
+        p.A = (const char*)A; p.B = (const char*)B; p.C = C;
+        p.bias = nullptr; p.aux_in = nullptr; p.aux_out = nullptr; p.colsum = colsum;
+        p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ld_aux = 0;
+        p.M = M; p.N = N; p.K = K;
+        p.out_dtype = MAEST_F32; p.epi = MAEST_EPI_ATOMIC; p.vec_ok = 0;
+        p.tiles_m = (M + 127) / 128;
+        p.tiles_n = (N + 127) / 128;
+        p.k_slices_per_split = per;
+        p.ws = use_ws ? (float*)workspace : nullptr;
+        if (use_ws) return dtype == MAEST_BF16 ? launch_gemm_tn_ws<bf16_t>(p, splits, (hipStream_t)stream)
+                                               : launch_gemm_tn_ws<float>(p, splits, (hipStream_t)stream);
+        return dtype == MAEST_BF16 ? launch_gemm_tn<bf16_t>(p, splits, (hipStream_t)stream)
+                                   : launch_gemm_tn<float>(p, splits, (hipStream_t)stream);
     }
     if (split_k == 0) {
         const int t = ((M + 127) / 128) * ((N + 127) / 128);
@@ -737,7 +868,7 @@ extern "C" int maest_gemm_tn_ws(const void* A, int64_t lda, const void* B, int64
     p.bias = nullptr; p.aux_in = nullptr; p.aux_out = nullptr; p.colsum = colsum;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.ld_aux = 0;
     p.M = M; p.N = N; p.K = K;
-    p.out_dtype = MAEST_F32; p.epi = MAEST_EPI_ATOMIC; p.vec_ok = 0;
+    p.out_dtype = MAEST_F32; p.epi = MAEST_EPI_ATOMIC; p.vec_ok = 0; p.ws = nullptr;
     p.tiles_m = (M + 127) / 128;
     p.tiles_n = (N + 127) / 128;
     const int ks = 128 / elt;

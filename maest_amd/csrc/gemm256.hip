@@ -955,7 +955,11 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTn256Params p) {
     }
     if (do_colsum) {
         const float tot = cs + __shfl_xor(cs, 32, 64);     // merge the two k halves
-        if (lane < 32) unsafeAtomicAdd(p.colsum + i0 + wm * 128 + wn * 32 + lane, tot);
+        if (p.cs_ws != nullptr) {      // ordered form: one row of partials per (split, j-tile), summed by tn256_colsum_reduce_kernel
+            if (lane < 32) p.cs_ws[((int64_t)split * p.tiles_n + tile_j) * p.M + i0 + wm * 128 + wn * 32 + lane] = tot;
+        } else if (lane < 32) {
+            unsafeAtomicAdd(p.colsum + i0 + wm * 128 + wn * 32 + lane, tot);
+        }
     }
 }
 
@@ -964,17 +968,20 @@ __global__ __launch_bounds__(512) void gemm_tn256_kernel(GemmTn256Params p) {
 // instruction, four splits in flight) and adds the sums to C as the accumulator layout has them -- for a fixed register the lanes of
 // a half-wave hold 32 consecutive columns of one row, i.e. lane-linear 128-byte runs, which cost their bytes
 // (scratch/probe/store_issue.hip).  No LDS, 40 registers: it fits beside any other kernel's workgroups.
+// ORDER (documented in include/maest_hip.h): s = 0; s += partial[split] for split = 0, 1, ...; C = C + s -- the destination last.
+// OW: the layout gemm_tn256o_kernel leaves (four waves of 4 x 4 blocks) instead of gemm_tn256_kernel's (eight waves of 4 x 2).
+template <bool OW>
 __global__ __launch_bounds__(64) void tn256_reduce_kernel(const float* __restrict__ ws, float* __restrict__ C, int64_t ldc, int ntiles,
                                                           int tiles_n, int split_k) {
     const int lane = threadIdx.x;
-    const int ab = blockIdx.x & 7, wave = (blockIdx.x >> 3) & 7, tile = blockIdx.x >> 6;
-    const int a = ab >> 1, b = ab & 1;
-    const int wm = wave >> 2, wn = wave & 3;
+    const int ab = OW ? (blockIdx.x & 15) : (blockIdx.x & 7), wave = OW ? ((blockIdx.x >> 4) & 3) : ((blockIdx.x >> 3) & 7), tile = blockIdx.x >> 6;
+    const int a = OW ? (ab >> 2) : (ab >> 1), b = OW ? (ab & 3) : (ab & 1);
+    const int wm = OW ? (wave >> 1) : (wave >> 2), wn = OW ? (wave & 1) : (wave & 3);
     const int tile_i = tile / tiles_n, tile_j = tile - tile_i * tiles_n;
     f32x4_t s[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) s[q] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* src = ws + ((int64_t)tile * 8 + wave) * 8192 + (ab * 4) * 256 + lane * 4;
+    const float* src = ws + ((int64_t)tile * (OW ? 4 : 8) + wave) * (OW ? 16384 : 8192) + (ab * 4) * 256 + lane * 4;
     const int64_t step = (int64_t)ntiles * 8 * 8192;
     int sp = 0;
     for (; sp + 4 <= split_k; sp += 4) {          // four splits' loads in flight, added in split order
@@ -995,12 +1002,32 @@ __global__ __launch_bounds__(64) void tn256_reduce_kernel(const float* __restric
         for (int q = 0; q < 4; ++q) s[q] += __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(src + q * 256));
         src += step;
     }
-    float* cp = C + ((int64_t)tile_i * 256 + wm * 128 + a * 32) * ldc + tile_j * 256 + wn * 64 + b * 32 + (lane & 31);
+    float* cp = C + ((int64_t)tile_i * 256 + wm * 128 + a * 32) * ldc + tile_j * 256 + (OW ? wn * 128 : wn * 64) + b * 32 + (lane & 31);
     float old[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) old[r] = cp[(int64_t)frag_row(r, lane) * ldc];
 #pragma unroll
     for (int r = 0; r < 16; ++r) cp[(int64_t)frag_row(r, lane) * ldc] = old[r] + s[r >> 2][r & 3];
+}
+
+// colsum[m] += sum of the n rows of partials the 256-tile kernels left in cs_ws ([split][tile_j][M]), ascending -- split-major, the
+// j-tiles of a split in tile order --, the destination last.  One thread per element.
+__global__ __launch_bounds__(256) void tn256_colsum_reduce_kernel(const float* __restrict__ cs_ws, float* __restrict__ colsum, int M, int n) {
+    const int m = blockIdx.x * 256 + threadIdx.x;
+    if (m >= M) return;
+    const float* src = cs_ws + m;
+    float s = 0.0f;
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {
+        const float v0 = src[0], v1 = src[M], v2 = src[2 * (int64_t)M], v3 = src[3 * (int64_t)M];
+        s += v0; s += v1; s += v2; s += v3;
+        src += 4 * (int64_t)M;
+    }
+    for (; i < n; ++i) {
+        s += src[0];
+        src += M;
+    }
+    colsum[m] = colsum[m] + s;
 }
 
 // split_k, K slices per split and workgroup count of the 256-tile TN kernel for a shape; false when it does not take the shape
@@ -1026,8 +1053,26 @@ static bool tn256_plan(int dtype, int M, int N, int K, int split_k, int* splits,
 // that has no workspace form (or a single split)
 int64_t gemm_tn256_workspace_bytes(int dtype, int M, int N, int K, int split_k) {
     int splits = 1, per = 0;
-    if (option(MAEST_OPT_TN_REDUCE) == 0 || !tn256_plan(dtype, M, N, K, split_k, &splits, &per) || splits < 2) return 0;
-    return (int64_t)splits * (M / 256) * (N / 256) * 65536 * (int64_t)sizeof(float);
+    const bool ordered = option(MAEST_OPT_DETERMINISTIC) != 0;     // partials of C AND of colsum
+    if ((option(MAEST_OPT_TN_REDUCE) == 0 && !ordered) || !tn256_plan(dtype, M, N, K, split_k, &splits, &per) || splits < 2) return 0;
+    const int64_t c_bytes = (int64_t)splits * (M / 256) * (N / 256) * 65536 * (int64_t)sizeof(float);
+    return ordered ? c_bytes + (int64_t)splits * (N / 256) * M * (int64_t)sizeof(float) : c_bytes;
+}
+
+// the reduce launches behind a 256-tile kernel that wrote its partials to p.ws (and p.cs_ws)
+static int launch_tn256_reduce(const GemmTn256Params& p, int split_k, bool ow, hipStream_t stream) {
+    const int ntiles = p.tiles_m * p.tiles_n;
+    if (ow)
+        hipLaunchKernelGGL(tn256_reduce_kernel<true>, dim3(ntiles * 64), dim3(64), 0, stream, (const float*)p.ws, p.C, p.ldc, ntiles,
+                           p.tiles_n, split_k);
+    else
+        hipLaunchKernelGGL(tn256_reduce_kernel<false>, dim3(ntiles * 64), dim3(64), 0, stream, (const float*)p.ws, p.C, p.ldc, ntiles,
+                           p.tiles_n, split_k);
+    int rc = check_launch("maest_gemm_tn(256, reduce)");
+    if (rc != MAEST_OK || p.cs_ws == nullptr || p.colsum == nullptr) return rc;
+    hipLaunchKernelGGL(tn256_colsum_reduce_kernel, dim3((p.M + 255) / 256), dim3(256), 0, stream, (const float*)p.cs_ws, p.colsum, p.M,
+                       split_k * p.tiles_n);
+    return check_launch("maest_gemm_tn(256, colsum reduce)");
 }
 
 template <typename T, bool X3 = false>
@@ -1039,9 +1084,7 @@ static int launch_tn256(GemmTn256Params& p, int split_k, hipStream_t stream) {
     hipLaunchKernelGGL((gemm_tn256_kernel<T, X3>), dim3(ntiles * split_k), dim3(512), G2_SMEM, stream, p);
     const int rc = check_launch("maest_gemm_tn(256)");
     if (rc != MAEST_OK || p.ws == nullptr) return rc;
-    hipLaunchKernelGGL(tn256_reduce_kernel, dim3(ntiles * 64), dim3(64), 0, stream, (const float*)p.ws, p.C, p.ldc, ntiles, p.tiles_n,
-                       split_k);
-    return check_launch("maest_gemm_tn(256, reduce)");
+    return launch_tn256_reduce(p, split_k, false, stream);
 }
 
 // Called by maest_gemm_tn; returns -1 when the shape does not qualify.  split_k <= 0 = automatic.  ws / ws_bytes: optional
@@ -1059,10 +1102,23 @@ int gemm_tn256_try(const void* A, int64_t lda, const void* B, int64_t ldb, int d
     p.tiles_m = M / 256;
     p.tiles_n = N / 256;
     p.k_slices_per_split = per;
-    const int64_t need = (int64_t)split_k * p.tiles_m * p.tiles_n * 65536 * (int64_t)sizeof(float);
-    const bool use_ws = ws != nullptr && split_k >= 2 && ws_bytes >= need && option(MAEST_OPT_TN_REDUCE) != 0 &&
+    const bool ordered = option(MAEST_OPT_DETERMINISTIC) != 0;
+    const int64_t c_need = (int64_t)split_k * p.tiles_m * p.tiles_n * 65536 * (int64_t)sizeof(float);
+    const int64_t need = ordered ? c_need + (int64_t)split_k * p.tiles_n * M * (int64_t)sizeof(float) : c_need;
+    const bool use_ws = ws != nullptr && split_k >= 2 && ws_bytes >= need && (ordered || option(MAEST_OPT_TN_REDUCE) != 0) &&
                         ((uintptr_t)ws % 16) == 0 && ((uintptr_t)C % 16) == 0 && (ldc % 4) == 0;
     p.ws = use_ws ? (float*)ws : nullptr;
+    p.cs_ws = (use_ws && ordered) ? (float*)ws + c_need / (int64_t)sizeof(float) : nullptr;
+    if (ordered) {
+        // MAEST_OPT_DETERMINISTIC: without the workspace (or with a single split, whose column sums still have one writer per j-tile)
+        // the shape goes to gemm_tn_kernel's one-writer form (gemm.hip); with it, bf16 operands keep the one-wave-per-SIMD kernel
+        if (!use_ws) return -1;
+        if (!x3 && dtype == MAEST_BF16 && option(MAEST_OPT_GEMM_VARIANT) != 3 && gemm_tn256o_available() &&
+            (int64_t)K * lda * 2 < ((int64_t)1 << 31) && (int64_t)K * ldb * 2 < ((int64_t)1 << 31)) {
+            const int rc = gemm_tn256o_launch(p, split_k, stream);
+            return rc != MAEST_OK ? rc : launch_tn256_reduce(p, split_k, true, stream);
+        }
+    }
     // bf16 operands, atomic combine: the one-wave-per-SIMD kernel (gemm_tn_ow.hip; 32-bit slice offsets); MAEST_OPT_GEMM_VARIANT = 3
     // keeps the 8-wave kernel (A/B, tests)
     if (!x3 && dtype == MAEST_BF16 && !use_ws && option(MAEST_OPT_GEMM_VARIANT) != 3 && gemm_tn256o_available() &&

@@ -184,8 +184,11 @@ struct GemmTn256Params {
     int tiles_m, tiles_n;
     int k_slices_per_split, split_k;
     float* ws;      // NULL: the split-K partials are added to C with fp32 atomics; else [split][tile][wave][32 chunks][64 lanes][4] fp32
+                    // (gemm_tn256o_kernel: [split][tile][wave][64 chunks][64 lanes][4] -- the same 65536 floats per split and tile)
+    float* cs_ws;   // NULL: the column-sum partials are added to colsum with fp32 atomics; else [split][tile_j][M] fp32 (MAEST_OPT_DETERMINISTIC)
 };
-// gemm_tn_ow.hip: the one-wave-per-SIMD 256 x 256 wgrad kernel (bf16 operands, atomic split-K combine: p.ws == NULL)
+// gemm_tn_ow.hip: the one-wave-per-SIMD 256 x 256 wgrad kernel (bf16 operands; atomic split-K combine, or -- p.ws / p.cs_ws -- the
+// partials as they sit in a0 .. a255 for tn256_reduce_kernel<true>)
 int gemm_tn256o_launch(GemmTn256Params& p, int split_k, hipStream_t stream);
 bool gemm_tn256o_available();   // false in a build whose register audit failed (maest_amd/build.py): the 8-wave kernel serves
 

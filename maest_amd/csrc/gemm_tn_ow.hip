@@ -15,7 +15,9 @@
 //     old (lgkmcnt(0) costs nothing), behind it the next slice is read and this slice's buffer is refilled;
 //   * the bias gradient is v_dot2c_f32_bf16 of the A fragments against a pair of ones (4 accumulators per 32-column block so that
 //     no two consecutive ones depend on each other), on the slices that are this tile's turn;
-//   * the split-K partials leave by fp32 atomics straight from the accumulator registers.
+//   * the split-K partials leave by fp32 atomics straight from the accumulator registers -- or, given a workspace (the ordered combine of
+//     MAEST_OPT_DETERMINISTIC), by 16-byte stores as they sit in a0 .. a255, the column sums as one row per (split, j-tile):
+//     gemm256.hip's tn256_reduce_kernel<true> / tn256_colsum_reduce_kernel add them up in split order.
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -423,15 +425,49 @@ __global__ __launch_bounds__(256, 1) void gemm_tn256o_kernel(GemmTn256Params p) 
         flush(a_tag, integral_constant<int, 0>{}, cb); flush(a_tag, integral_constant<int, 1>{}, cb);
         flush(a_tag, integral_constant<int, 2>{}, cb); flush(a_tag, integral_constant<int, 3>{}, cb);
     };
-    flush_row(std::integral_constant<int, 0>{});
-    flush_row(std::integral_constant<int, 1>{});
-    flush_row(std::integral_constant<int, 2>{});
-    flush_row(std::integral_constant<int, 3>{});
+    // Workspace form: block (A, B) leaves as four lane-linear 16-byte stores of 1 KiB -- [split][tile][wave][16 blocks][4][64 lanes][4] fp32, a
+    // layout private to this kernel and tn256_reduce_kernel<true> (gemm256.hip), which adds the splits up in order.
+    auto park = [&](auto a_tag, auto b_tag, float* wbase) {
+        constexpr int A = decltype(a_tag)::value, B = decltype(b_tag)::value;
+        const f32x16_t t = tw_acc_read<A, B>(c);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const f32x4_t v = {t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]};
+            __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(wbase + (B * 4 + q) * 256));
+        }
+    };
+    auto park_row = [&](auto a_tag) {
+        using std::integral_constant;
+        constexpr int A = decltype(a_tag)::value;
+        float* wb = p.ws + ((int64_t)(split * ntiles + tile) * 4 + wave) * 16384 + A * 4096 + lane * 4;
+#if TW_DEV
+        asm volatile("" : "+v"(wb));       // (one address per row of blocks, as flush_row)
+#endif
+        park(a_tag, integral_constant<int, 0>{}, wb); park(a_tag, integral_constant<int, 1>{}, wb);
+        park(a_tag, integral_constant<int, 2>{}, wb); park(a_tag, integral_constant<int, 3>{}, wb);
+    };
+    if (p.ws != nullptr) {
+        park_row(std::integral_constant<int, 0>{});
+        park_row(std::integral_constant<int, 1>{});
+        park_row(std::integral_constant<int, 2>{});
+        park_row(std::integral_constant<int, 3>{});
+    } else {
+        flush_row(std::integral_constant<int, 0>{});
+        flush_row(std::integral_constant<int, 1>{});
+        flush_row(std::integral_constant<int, 2>{});
+        flush_row(std::integral_constant<int, 3>{});
+    }
     if (do_colsum) {
         // this wave summed blocks 2 wn, 2 wn + 1 of its i half: column lane & 31, this lane's k half
         const float t0 = tw_colsum_get<0>(c), t1 = tw_colsum_get<1>(c);
         const float s0 = t0 + __shfl_xor(t0, 32, 64), s1 = t1 + __shfl_xor(t1, 32, 64);
-        if (lane < 32) {
+        if (p.cs_ws != nullptr) {      // ordered form: one row of partials per (split, j-tile), every entry written
+            float* cw = p.cs_ws + ((int64_t)split * p.tiles_n + tile_j) * p.M + i0 + wm * 128 + (2 * wn) * 32 + lane;
+            if (lane < 32) {
+                cw[0] = s0;
+                cw[32] = s1;
+            }
+        } else if (lane < 32) {
             unsafeAtomicAdd(p.colsum + i0 + wm * 128 + (2 * wn) * 32 + lane, s0);
             unsafeAtomicAdd(p.colsum + i0 + wm * 128 + (2 * wn + 1) * 32 + lane, s1);
         }

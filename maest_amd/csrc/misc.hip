@@ -201,6 +201,23 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ src, 
     unsafeAtomicAdd(out + c, s);
 }
 
+// The ordered form (MAEST_OPT_DETERMINISTIC): one thread per column walks ALL rows in ascending order, chunk by chunk as above (a chunk
+// of 512 rows is summed from 0, the chunk sums are added in ascending order), and adds the total to out[c] once.
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_ordered_kernel(const T* __restrict__ src, int64_t ld, int rows, int cols,
+                                                             float* __restrict__ out) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    float tot = 0.0f;
+    for (int r0 = 0; r0 < rows; r0 += 512) {
+        const int r_end = r0 + 512 < rows ? r0 + 512 : rows;
+        float s = 0.0f;
+        for (int r = r0; r < r_end; ++r) s += elem_traits<T>::to_f32(src[(int64_t)r * ld + c]);
+        tot += s;
+    }
+    out[c] = out[c] + tot;
+}
+
 // ---- BCE with logits (mean), optional label mixup.  The loss is a sum in a FIXED order, so that the same logits give the same
 // loss bit for bit: per-workgroup partials (per-thread strided sums, wave butterflies, four wave partials added by thread 0), then
 // one wave adds the partials in index order.  (Rounds 1-3 added the workgroup partials with one atomic each: their order, and with it
@@ -428,6 +445,14 @@ extern "C" int maest_colsum(const void* src, int64_t ld, int rows, int cols, int
     MAEST_REQUIRE(src && out, "maest_colsum: null pointer");
     MAEST_REQUIRE(rows > 0 && cols > 0 && ld >= cols, "maest_colsum: bad shape");
     MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16, "maest_colsum: bad dtype");
+    if (option(MAEST_OPT_DETERMINISTIC) != 0) {
+        const dim3 g1((cols + 255) / 256);
+        if (dtype == MAEST_BF16)
+            hipLaunchKernelGGL(colsum_ordered_kernel<bf16_t>, g1, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, ld, rows, cols, out);
+        else
+            hipLaunchKernelGGL(colsum_ordered_kernel<float>, g1, dim3(256), 0, (hipStream_t)stream, (const float*)src, ld, rows, cols, out);
+        return check_launch("maest_colsum(ordered)");
+    }
     dim3 grid((cols + 255) / 256, (rows + 511) / 512);
     if (dtype == MAEST_BF16)
         hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)src, ld,

@@ -130,6 +130,10 @@ __global__ __launch_bounds__(256) void add_layernorm_fwd_kernel(const float* __r
 }
 
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma ;  dgamma += dy * xhat ; dbeta += dy
+// MODE 0: the whole pass, dgamma / dbeta by one atomic per column and workgroup.  The ordered form (MAEST_OPT_DETERMINISTIC) runs MODE 1 --
+// the same pass, but rows < row_split of dx_out / dx_lp are not written and the workgroup's partials are parked in dx_out instead
+// ([workgroup][2][768] = rows [0, 2 * workgroups)) --, ln_park_reduce_kernel, and MODE 2: rows < row_split only, no partials.
+template <int MODE>
 __global__ __launch_bounds__(256, 5) void layernorm_bwd_kernel(const void* __restrict__ dy, int64_t lddy, int dy_dtype,
                                                             const float* __restrict__ x, int64_t ldx,
                                                             const float* __restrict__ gamma,
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(256, 5) void layernorm_bwd_kernel(const void* __res
                                                             const float* __restrict__ dres, float* __restrict__ dx_out,
                                                             void* __restrict__ dx_lp, int dx_lp_dtype,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                            int rows, int n_tok, int n_head) {
+                                                            int rows, int n_tok, int n_head, int row_split) {
     // n_head > 0: `dres` is COMPACT -- [clips][n_head][768], the residual gradient of the first n_head tokens of every
     // clip of n_tok tokens, zero for the others (the last block of the network, whose patch tokens feed nothing)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -150,7 +154,7 @@ __global__ __launch_bounds__(256, 5) void layernorm_bwd_kernel(const void* __res
     float ag[12], ab[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) { ag[i] = 0.0f; ab[i] = 0.0f; }
-    for (int row = blockIdx.x * 4 + wave; row < rows; row += gridDim.x * 4) {
+    for (int row = blockIdx.x * 4 + wave; row < (MODE == 2 ? row_split : rows); row += gridDim.x * 4) {
         float xv[12], dv[12];
         ln_load_row(x + (int64_t)row * ldx, lane, xv);
 #pragma unroll
@@ -172,6 +176,7 @@ __global__ __launch_bounds__(256, 5) void layernorm_bwd_kernel(const void* __res
             xv[i] = xh;
             dv[i] = g;
         }
+        if (MODE == 1 && row < row_split) continue;       // (wave-uniform: these rows hold the parked partials until MODE 2 writes them)
         s1 = wave_sum(s1) * (1.0f / LN_COLS);
         s2 = wave_sum(s2) * (1.0f / LN_COLS);
 #pragma unroll
@@ -197,6 +202,7 @@ __global__ __launch_bounds__(256, 5) void layernorm_bwd_kernel(const void* __res
             if (dx_lp != nullptr) store_row4(dx_lp, dx_lp_dtype, off, o[0], o[1], o[2], o[3]);
         }
     }
+    if (MODE == 2) return;
     // block reduce of the per-wave dgamma / dbeta partials, then one atomic per column per block
 #pragma unroll
     for (int i = 0; i < LN_VEC; ++i)
@@ -214,8 +220,49 @@ __global__ __launch_bounds__(256, 5) void layernorm_bwd_kernel(const void* __res
             sg += red[(w * 2 + 0) * LN_COLS + c];
             sb += red[(w * 2 + 1) * LN_COLS + c];
         }
-        unsafeAtomicAdd(dgamma + c, sg);
-        unsafeAtomicAdd(dbeta + c, sb);
+        if (MODE == 1) {
+            dx_out[((int64_t)blockIdx.x * 2 + 0) * LN_COLS + c] = sg;
+            dx_out[((int64_t)blockIdx.x * 2 + 1) * LN_COLS + c] = sb;
+        } else {
+            unsafeAtomicAdd(dgamma + c, sg);
+            unsafeAtomicAdd(dbeta + c, sb);
+        }
+    }
+}
+
+// dgamma / dbeta += the sum of the partials layernorm_bwd_kernel<1> parked ([blocks][2][768]), in a FIXED order: 16 runs of
+// ceil(blocks / 16) consecutive workgroups, each summed in ascending order by one thread, then the 16 run sums in ascending order, then
+// the destination.  Workgroup = 16 columns of [dgamma | dbeta] x 16 runs; grid 2 * 768 / 16.
+__global__ __launch_bounds__(256) void ln_park_reduce_kernel(const float* __restrict__ park, int blocks, float* __restrict__ dgamma,
+                                                             float* __restrict__ dbeta) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float (*part)[17] = reinterpret_cast<float (*)[17]>(smem);      // [16 runs][16 columns, padded]
+    const int cl = threadIdx.x & 15, run = threadIdx.x >> 4;
+    const int col = blockIdx.x * 16 + cl;                  // 0 .. 1535: [dgamma | dbeta]
+    const int which = col >= LN_COLS ? 1 : 0, c = col - which * LN_COLS;
+    const int per = (blocks + 15) / 16;
+    const int b0 = run * per;
+    const int b1 = b0 + per < blocks ? b0 + per : blocks;
+    const float* src = park + ((int64_t)b0 * 2 + which) * LN_COLS + c;
+    float s = 0.0f;
+    int b = b0;
+    for (; b + 4 <= b1; b += 4) {
+        const float v0 = src[0], v1 = src[2 * LN_COLS], v2 = src[4 * LN_COLS], v3 = src[6 * LN_COLS];
+        s += v0; s += v1; s += v2; s += v3;
+        src += 8 * LN_COLS;
+    }
+    for (; b < b1; ++b) {
+        s += src[0];
+        src += 2 * LN_COLS;
+    }
+    part[run][cl] = s;
+    __syncthreads();
+    if (run == 0) {
+        float t = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t += part[r][cl];
+        float* dst = (which ? dbeta : dgamma) + c;
+        *dst = *dst + t;
     }
 }
 
@@ -383,9 +430,27 @@ extern "C" int maest_layernorm_bwd_headres(const void* dy, int64_t lddy, int dy_
     int blocks = (rows + 3) / 4;
     const int cap = option(MAEST_OPT_LN_BWD_BLOCKS);     // grid-stride cap: per-block dgamma/dbeta partials vs waves in flight
     if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(blocks), dim3(256), 4 * 2 * LN_COLS * 4, (hipStream_t)stream, dy,
+    if (blocks < 1) blocks = 1;
+    if (option(MAEST_OPT_DETERMINISTIC) != 0 && blocks > 1) {
+        // ordered dgamma / dbeta (include/maest_hip.h: MAEST_OPT_DETERMINISTIC).  blocks >= 2 implies 2 * blocks <= rows.
+        if (dx_out == nullptr) {        // nowhere to park: one workgroup, one add per column
+            hipLaunchKernelGGL(layernorm_bwd_kernel<0>, dim3(1), dim3(256), 4 * 2 * LN_COLS * 4, (hipStream_t)stream, dy, lddy, dy_dtype, x,
+                               ldx, gamma, mean, rstd, dres, dx_out, dx_lp, dx_lp_dtype, dgamma, dbeta, rows, n_tok > 0 ? n_tok : 1, n_head, 0);
+            return check_launch("maest_layernorm_bwd");
+        }
+        const int row_split = 2 * blocks;
+        hipLaunchKernelGGL(layernorm_bwd_kernel<1>, dim3(blocks), dim3(256), 4 * 2 * LN_COLS * 4, (hipStream_t)stream, dy, lddy, dy_dtype, x,
+                           ldx, gamma, mean, rstd, dres, dx_out, dx_lp, dx_lp_dtype, dgamma, dbeta, rows, n_tok > 0 ? n_tok : 1, n_head, row_split);
+        hipLaunchKernelGGL(ln_park_reduce_kernel, dim3(2 * LN_COLS / 16), dim3(256), 16 * 17 * 4, (hipStream_t)stream, (const float*)dx_out, blocks,
+                           dgamma, dbeta);
+        hipLaunchKernelGGL(layernorm_bwd_kernel<2>, dim3((row_split + 3) / 4), dim3(256), 4 * 2 * LN_COLS * 4, (hipStream_t)stream, dy, lddy,
+                           dy_dtype, x, ldx, gamma, mean, rstd, dres, dx_out, dx_lp, dx_lp_dtype, dgamma, dbeta, rows, n_tok > 0 ? n_tok : 1,
+                           n_head, row_split);
+        return check_launch("maest_layernorm_bwd(ordered)");
+    }
+    hipLaunchKernelGGL(layernorm_bwd_kernel<0>, dim3(blocks), dim3(256), 4 * 2 * LN_COLS * 4, (hipStream_t)stream, dy,
                        lddy, dy_dtype, x, ldx, gamma, mean, rstd, dres, dx_out, dx_lp, dx_lp_dtype, dgamma, dbeta,
-                       rows, n_tok > 0 ? n_tok : 1, n_head);
+                       rows, n_tok > 0 ? n_tok : 1, n_head, 0);
     return check_launch("maest_layernorm_bwd");
 }
 
@@ -418,7 +483,8 @@ extern "C" int maest_head_pool_bwd(const float* d_cls, const float* d_dist, cons
         set_error("maest_head_pool_bwd: hipMemsetAsync failed");
         return MAEST_ERR_LAUNCH;
     }
-    const int blocks = (2 * B + 3) / 4 < 32 ? (2 * B + 3) / 4 : 32;
+    // (MAEST_OPT_DETERMINISTIC: one workgroup -- its four waves' partials are summed in wave order and added once per column)
+    const int blocks = option(MAEST_OPT_DETERMINISTIC) != 0 ? 1 : ((2 * B + 3) / 4 < 32 ? (2 * B + 3) / 4 : 32);
     hipLaunchKernelGGL(head_pool_bwd_kernel, dim3(blocks), dim3(256), 4 * 2 * LN_COLS * 4, (hipStream_t)stream, d_cls, d_dist,
                        d_feat, x, B, N, gamma, mean, rstd, dx, dgamma, dbeta);
     return check_launch("maest_head_pool_bwd");

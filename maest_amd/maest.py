@@ -616,13 +616,19 @@ class _Engine:
         return outs, ctx
 
     # ---- backward ---------------------------------------------------------------------------
+    def _deterministic_form(self):
+        """The ordered gradient reductions for a pass, as a per-thread override like _gemm_form: two models in one process, one of them
+        deterministic, never change each other's launches.  None (follow the library switch): nothing is set."""
+        mode = self.m.deterministic_mode()
+        return contextlib.nullcontext() if mode is None else ops.thread_options(deterministic=mode)
+
     def backward(self, ctx, grads_out, sink=None):
         if ctx.get("f16"):     # recorded by libmaest_hip_f16.so: its 16-bit tensors are IEEE half, the backward is that build's too (this thread's calls)
             from . import _lib as _L
-            with _L.flavour("f16"), self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs):
+            with _L.flavour("f16"), self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs), self._deterministic_form():
                 G = self._backward(ctx, grads_out, sink)
         else:
-            with self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs):
+            with self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs), self._deterministic_form():
                 G = self._backward(ctx, grads_out, sink)
         self._step_done(ctx["cols"].device)
         return G
@@ -930,6 +936,12 @@ def _check_rates(drop_rate, attn_drop_rate, drop_path_rate):
                                   "not built (drop_rate and drop_path_rate are)")
 
 
+def _check_deterministic(value):
+    if value is not None and not isinstance(value, bool):
+        raise ValueError(f"deterministic must be None (follow torch.use_deterministic_algorithms / MAEST_DETERMINISTIC), True or False, "
+                         f"got {value!r}")
+
+
 def regulariser_seed(initial_seed: int, rank: int = 0) -> int:
     """The 64-bit mask seed a model derives when none was set: a pure function of torch.initial_seed() and the process's rank in the
     default process group, so that data-parallel ranks that share a torch seed do not share masks (splitmix64 finaliser of
@@ -948,9 +960,11 @@ class MAEST(nn.Module):
                  s_patchout_f_interleaved=0, s_patchout_t_indices=(), s_patchout_t_interleaved=0,
                  img_size=(96, 625), patch_size=16, stride=10, in_chans=1, num_classes=400, embed_dim=768,
                  depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True, distilled=True, distilled_type="mean",
-                 precision="auto", drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, _skip_init: bool = False):
+                 precision="auto", drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0, *, deterministic=None,
+                 _skip_init: bool = False):
         super().__init__()
         _check_rates(drop_rate, attn_drop_rate, drop_path_rate)
+        _check_deterministic(deterministic)
         self._skip_init = bool(_skip_init)      # clone_weights(): the twin's parameters are copies, not draws
         self._init_kwargs = dict(u_patchout=u_patchout, s_patchout_t=s_patchout_t, s_patchout_f=s_patchout_f,
                                  s_patchout_f_indices=s_patchout_f_indices,
@@ -961,7 +975,7 @@ class MAEST(nn.Module):
                                  embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
                                  qkv_bias=qkv_bias, distilled=distilled, distilled_type=distilled_type,
                                  precision=precision, drop_rate=drop_rate, attn_drop_rate=attn_drop_rate,
-                                 drop_path_rate=drop_path_rate)
+                                 drop_path_rate=drop_path_rate, deterministic=deterministic)
         if embed_dim != EMBED_DIM or num_heads != NUM_HEADS or patch_size != PATCH or in_chans != 1:
             raise NotImplementedError("maest_amd kernels are specialised for the MAEST geometry: "
                                       "embed_dim=768, 12 heads x 64, 16x16 patches, mono input")
@@ -984,6 +998,10 @@ class MAEST(nn.Module):
         self.drop_rate = float(drop_rate)
         self.attn_drop_rate = float(attn_drop_rate)
         self.drop_path_rate = float(drop_path_rate)
+        # Bit-reproducible backward (include/maest_hip.h: MAEST_OPT_DETERMINISTIC): a plain attribute, read at every backward.  None follows
+        # torch.are_deterministic_algorithms_enabled() or the library switch (ops.set_option("deterministic", 1) / MAEST_DETERMINISTIC=1);
+        # True / False override both for this model's passes.
+        self.deterministic = deterministic
         self._reg_seed = None        # set_regulariser_seed(), else derived at the first regularised forward
         self._reg_state = {}         # {device: int32 [4] = seed lo, seed hi, step, 0} (include/maest_hip.h), not a registered buffer
         if num_classes == 400:
@@ -1027,7 +1045,7 @@ class MAEST(nn.Module):
         # configuration changed after construction travels too (patchout switched off for evaluation, numeric mode, engine
         # switches) -- run-time state does not, and neither does graph replay: a twin (SWA average, teacher) captures graphs,
         # with their private memory pools, only when its owner calls enable_hip_graph() on it
-        for k in ("precision", "drop_rate", "attn_drop_rate", "drop_path_rate", "u_patchout", "s_patchout_t", "s_patchout_f", "s_patchout_f_indices",
+        for k in ("precision", "drop_rate", "attn_drop_rate", "drop_path_rate", "deterministic", "u_patchout", "s_patchout_t", "s_patchout_f", "s_patchout_f_indices",
                   "s_patchout_f_interleaved", "s_patchout_t_indices", "s_patchout_t_interleaved"):
             setattr(twin, k, getattr(self, k))
         twin._engine.head_tail = self._engine.head_tail
@@ -1048,6 +1066,22 @@ class MAEST(nn.Module):
         twin = self.clone_weights()
         memo[id(self)] = twin
         return twin
+
+    # ---- bit-reproducible training ---------------------------------------------------------------
+    def deterministic_mode(self):
+        """What this model's backward passes run with: None = the library switch as it stands (self.deterministic is None and torch's
+        deterministic-algorithms flag is off), else 1 / 0 = a per-thread override for the pass.  Scope of the guarantee:
+        one process on one GPU, the same build, shapes and option values."""
+        _check_deterministic(self.deterministic)
+        if self.deterministic is None:
+            return 1 if torch.are_deterministic_algorithms_enabled() else None
+        return 1 if self.deterministic else 0
+
+    @property
+    def is_deterministic(self) -> bool:
+        """Whether a backward of this model, launched now from this thread, runs the ordered gradient reductions."""
+        mode = self.deterministic_mode()
+        return bool(ops.get_option("deterministic")) if mode is None else bool(mode)
 
     # ---- regularisers: dropout and stochastic depth ----------------------------------------------
     @property
@@ -1478,9 +1512,10 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
               s_patchout_f: int = 0, s_patchout_f_indices: tuple = (), s_patchout_f_interleaved: int = 0,
               s_patchout_t_indices: tuple = (), s_patchout_t_interleaved: int = 0, distilled_type: str = "mean",
               checkpoint: str = None, checkpoint_swa_weigts: bool = True, checkpoint_discard_head: bool = False,
-              precision: str = "auto", *, drop_rate: float = 0.0, drop_path_rate: float = 0.0):
+              precision: str = "auto", *, drop_rate: float = 0.0, drop_path_rate: float = 0.0, deterministic=None):
     """Same signature and semantics as the reference factory (models/maest.py:1467-1569), plus
-    ``precision`` (see the module docstring) and the keyword-only ``drop_rate`` / ``drop_path_rate`` of the MAEST constructor.
+    ``precision`` (see the module docstring) and the keyword-only ``drop_rate`` / ``drop_path_rate`` / ``deterministic`` of the MAEST
+    constructor.
     Returns the model in train mode, like the reference."""
     if arch not in _ARCH_DEFAULT_T:
         raise NotImplementedError(f"model {arch} not implemented")
@@ -1502,7 +1537,8 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
                   s_patchout_t_indices=s_patchout_t_indices, s_patchout_t_interleaved=s_patchout_t_interleaved,
                   img_size=(input_f, input_t), patch_size=16, stride=(stride_f, stride_t), in_chans=in_channels,
                   num_classes=n_classes, embed_dim=768, depth=12, num_heads=12, distilled=True,
-                  distilled_type=distilled_type, precision=precision, drop_rate=drop_rate, drop_path_rate=drop_path_rate)
+                  distilled_type=distilled_type, precision=precision, drop_rate=drop_rate, drop_path_rate=drop_path_rate,
+                  deterministic=deterministic)
     if checkpoint:
         state_dict = torch.load(checkpoint, map_location="cpu")["state_dict"]
         replace_str = "net_swa." if checkpoint_swa_weigts else ""

@@ -179,7 +179,8 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, colsum: Optiona
     # comes from torch's caching allocator on the CURRENT stream -- the stream the call runs on -- so its reuse is stream-ordered
     code = _mm_code(a.dtype, x3)
     nbytes = ctypes.c_int64(0)
-    if get_option("tn_reduce") != 0:         # (the default combines split-K partials with atomics: no scratch, no query)
+    # (the default combines split-K partials with atomics: no scratch, no query; "deterministic" orders C and colsum through the scratch)
+    if get_option("tn_reduce") != 0 or get_option("deterministic") != 0:
         call("maest_gemm_tn_workspace_bytes", code, M, N, K, split_k, ctypes.byref(nbytes))
     ws = torch.empty(nbytes.value, dtype=torch.uint8, device=a.device) if nbytes.value > 0 else None
     _timed_call("maest_gemm_tn", 2.0 * M * N * K, _p(a), a.stride(0), _p(b), b.stride(0), code, _p(out2),
