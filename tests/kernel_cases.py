@@ -12,6 +12,7 @@ and read back with f32(), which follow the calling thread's build; 16-bit tolera
 
 16-bit results of the GEMM epilogues, LayerNorm and the patch-embed backward are also held to the rounding bracket close16(): the stored value
 must be the round-to-nearest-even rounding of an fp32 value within a derived delta of an fp64 reference.
+The LayerNorm, head and loss kernels on rows where fp32 is hard, against bounds counted from their roundings: tests/norm_cases.py (section 7c).
 """
 import math
 

@@ -17,6 +17,7 @@ from maest_amd.module import Module
 from tests import deterministic_cases as DC
 from tests import guard
 from tests import kernel_cases as KC
+from tests import norm_cases as NC
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -123,6 +124,17 @@ def test_layernorm_head_and_embedding_cases_under_the_option(gemm_options):
         KC.case_patch_embed(DEV, BF, 5, 626, patchout=30, mix=True)
         gemm_options(ln_bwd_blocks=2)
         KC.case_layernorm(DEV, BF, 11)
+
+
+@pytest.mark.parametrize("flavour,dtype", [("bf16", torch.float32), ("bf16", BF), ("f16", BF)])
+def test_layernorm_bwd_on_hard_rows_under_the_option(flavour, dtype):
+    """tests/norm_cases.py: the parked form (ln_bwd_blocks default: 97 workgroups; 2: a workgroup walks 49 row groups)
+    and head_pool_bwd's single workgroup inside the bounds the counted roundings allow"""
+    with _flavour(flavour):
+        NC.case_layernorm_bwd(DEV, dtype, 64, deterministic=(1,))
+        if dtype == torch.float32:
+            with ops.thread_options(deterministic=1):
+                NC.case_head_pool(DEV)
 
 
 @pytest.mark.parametrize("B", [1, 3, 256])

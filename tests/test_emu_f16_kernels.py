@@ -10,6 +10,7 @@ from maest_amd import _lib, ops
 from tests import attention_cases as AC
 from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
+from tests import norm_cases as NC
 from tests.test_emu_grad_kernels import _case, _im2col_ref, _stripes
 
 BF = torch.bfloat16     # the 16-bit container tag of both builds
@@ -92,6 +93,15 @@ def test_emu_f16_colsum(emu16):
 def test_emu_f16_layernorm(emu16):
     """layernorm_fwd / add_layernorm_fwd / layernorm_bwd (16-bit dy in, 16-bit dx out), with the compact head-token form."""
     KC.controlled(KC.case_layernorm, emu16, BF, 11)
+
+
+def test_emu_f16_layernorm_on_hard_rows(emu16):
+    """tests/norm_cases.py in the half build: every LayerNorm entry point with a half y / delta / dy / dx_lp."""
+    with _lib.flavour("f16"):
+        NC.case_layernorm_fwd(emu16, BF, 4)
+        NC.case_add_layernorm_fwd(emu16, BF, 4)
+        NC.case_drop_add_layernorm_fwd(emu16, BF, 4, n_tok=9)
+        NC.case_layernorm_bwd(emu16, BF, 4, blocks=(None,), deterministic=(0,))
 
 
 def test_emu_f16_attention(emu16):

@@ -7,6 +7,7 @@ import torch
 from tests import attention_cases as AC
 from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
+from tests import norm_cases as NC
 
 DT = [torch.float32, torch.bfloat16]
 # The fp32-MFMA instantiations of the 256-row-tile GEMM kernels take 30-50 s each under the emulator (K = 2 per MFMA): the CPU suite runs
@@ -123,6 +124,32 @@ def test_emu_layernorm(emu, dtype):
     KC.case_layernorm(emu, dtype, 11)
 
 
+# tests/norm_cases.py (DESIGN.md section 7c): 4 rows per family and 3 loose ones = 27 rows, inside the bounds the roundings allow
+@pytest.mark.parametrize("dtype", DT)
+def test_emu_layernorm_fwd_on_hard_rows(emu, dtype):
+    NC.case_layernorm_fwd(emu, dtype, 4)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_emu_add_layernorm_fwd_on_hard_rows(emu, dtype):
+    NC.case_add_layernorm_fwd(emu, dtype, 4)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_emu_drop_add_layernorm_fwd_on_hard_rows(emu, dtype):
+    NC.case_drop_add_layernorm_fwd(emu, dtype, 4, n_tok=9)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_emu_layernorm_bwd_on_hard_rows(emu, dtype):
+    NC.case_layernorm_bwd(emu, dtype, 4, deterministic=(0,))
+
+
+def test_emu_layernorm_bwd_on_hard_rows_ordered_sums(emu):
+    """... under MAEST_OPT_DETERMINISTIC: the parked form (MODE 1, the reduction, MODE 2), two workgroups walking the 27 / 25 rows."""
+    NC.case_layernorm_bwd(emu, torch.bfloat16, 4, blocks=(2,), deterministic=(1,), eps_values=(1e-5,), modes=("no dres", "compact dres"))
+
+
 @pytest.mark.parametrize("dtype", DT)
 def test_emu_attention(emu, dtype):
     # bf16: two key tiles; fp32 (4x the emulated MFMAs): one tile here, its multi-tile path is the spike case below
@@ -231,6 +258,14 @@ def test_emu_head(emu):
 
 def test_emu_loss(emu):
     KC.case_loss(emu, 6, 50)
+
+
+def test_emu_head_pool_on_hard_rows(emu):
+    NC.case_head_pool(emu)
+
+
+def test_emu_loss_on_extreme_logits(emu):
+    NC.case_loss(emu, shapes=((7, 519), (6, 50)))
 
 
 def test_emu_spec_mask(emu):

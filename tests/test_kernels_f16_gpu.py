@@ -10,6 +10,7 @@ from maest_amd import _lib
 from tests import attention_cases as AC
 from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
+from tests import norm_cases as NC
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -86,6 +87,35 @@ def test_f16_transpose_and_casts():
 def test_f16_layernorm_and_colsum():
     KC.controlled(KC.case_layernorm, DEV, BF, 1123)
     KC.controlled(KC.case_loss, DEV, 64, 400)
+
+
+# tests/norm_cases.py in the half build: the bounds are those of the fp32 arithmetic, the 16-bit outputs are held to
+# the half rounding bracket
+def test_f16_layernorm_fwd_on_hard_rows():
+    with _lib.flavour("f16"):
+        NC.case_layernorm_fwd(DEV, BF, 64)
+
+
+def test_f16_add_layernorm_fwd_on_hard_rows():
+    with _lib.flavour("f16"):
+        NC.case_add_layernorm_fwd(DEV, BF, 64)
+
+
+def test_f16_drop_add_layernorm_fwd_on_hard_rows():
+    with _lib.flavour("f16"):
+        NC.case_drop_add_layernorm_fwd(DEV, BF, 64, n_tok=43)
+
+
+def test_f16_layernorm_bwd_on_hard_rows():
+    with _lib.flavour("f16"):
+        NC.case_layernorm_bwd(DEV, BF, 64, deterministic=(0,))
+
+
+def test_f16_head_pool_and_loss_on_hard_rows():
+    """fp32 kernels: the half build compiles the same sources"""
+    with _lib.flavour("f16"):
+        NC.case_head_pool(DEV)
+        NC.case_loss(DEV)
 
 
 @pytest.mark.parametrize("BN", [(2, 560), (3, 281), (1, 875), (1, 64), (1, 129)])

@@ -6,6 +6,7 @@ import torch
 from tests import attention_cases as AC
 from tests import epilogue_cases as EC
 from tests import kernel_cases as KC
+from tests import norm_cases as NC
 
 pytestmark = pytest.mark.gpu
 DT = [torch.float32, torch.bfloat16]
@@ -138,6 +139,39 @@ def test_transpose(dtype):
 @pytest.mark.parametrize("dtype", DT)
 def test_layernorm(dtype):
     KC.case_layernorm(DEV, dtype, 1123)
+
+
+# tests/norm_cases.py (DESIGN.md section 7c): 64 rows of every family and 3 loose ones in one tensor = 387 rows (not a multiple of the 4 rows of
+# a workgroup), both eps, inside the bounds the counted roundings allow; each prints the worst err / bound per output and family
+@pytest.mark.parametrize("dtype", DT)
+def test_layernorm_fwd_on_hard_rows(dtype):
+    NC.case_layernorm_fwd(DEV, dtype, 64)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_add_layernorm_fwd_on_hard_rows(dtype):
+    NC.case_add_layernorm_fwd(DEV, dtype, 64)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_drop_add_layernorm_fwd_on_hard_rows(dtype):
+    """... with its own copy of the statistics code: nothing dropped, and element keep 0.9 / path keep 0.8 at 43 and 2 rows per clip"""
+    NC.case_drop_add_layernorm_fwd(DEV, dtype, 64, n_tok=43)
+
+
+@pytest.mark.parametrize("dtype", DT)
+def test_layernorm_bwd_on_hard_rows(dtype):
+    """without dres, dense, compact (5, 2); ln_bwd_blocks default and 2 (the ordered form: tests/test_deterministic_gpu.py)"""
+    NC.case_layernorm_bwd(DEV, dtype, 64, deterministic=(0,))
+
+
+def test_head_pool_on_hard_rows():
+    NC.case_head_pool(DEV)
+
+
+def test_loss_on_extreme_logits():
+    """both launch forms of maest_bce_logits and maest_sigmoid_mean on logits tiled from 0, +-1e-8, +-1, +-20, +-87, +-89, +-104, +-1e4"""
+    NC.case_loss(DEV)
 
 
 @pytest.mark.parametrize("dtype", DT)
