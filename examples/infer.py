@@ -31,10 +31,17 @@ def main():
         logits, embeddings = model(audio)                       # 1-D audio: mel on the GPU, chunked into a batch
         _, emb7 = model(audio, transformer_block=6)             # cls + dist + mean token of block 6
         activations, labels = model.predict_labels(audio)
+        maps = model.attention_maps(audio, blocks=-1, heads="mean")     # softmax(q k^T * scale) of the last block, cls / dist rows
     top = np.argsort(activations)[::-1][:5]
     print("logits", tuple(logits.shape), "embeddings", tuple(embeddings.shape), "block-6 embedding", tuple(emb7.shape))
     for i in top:
         print(f"  {activations[i]:.3f}  {labels[i]}")
+    # where the cls token of the last block looks: its attention on the patch grid, summed over frequency, per time patch of chunk 0
+    last = max(maps.maps)
+    per_t = torch.nan_to_num(maps.to_grid(last, query=0)[0]).sum(0)          # [T']
+    best = torch.topk(per_t, 5).indices.tolist()
+    print(f"block {last} cls attention, top time patches of chunk 0 (of {maps.grid[1]}; 0.16 s apart):",
+          ", ".join(f"t={t} ({per_t[t].item():.4f})" for t in best))
 
 
 if __name__ == "__main__":

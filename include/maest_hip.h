@@ -276,7 +276,22 @@ int maest_layernorm_bwd_headres(const void* dy, int64_t lddy, int dy_dtype, cons
  * qkv: [B*N, 2304] with column = s*768 + h*64 + d  (s = 0,1,2 for q,k,v), exactly the layout the
  * reference's qkv Linear produces before its reshape/permute (:362-363).
  * out: [B*N, 768] (column = h*64 + d), i.e. the reference's (attn @ v).transpose(1,2).reshape(B,N,C).
- * lse: fp32 [B, 12, N] log-sum-exp of the scaled scores (saved for backward) or NULL. */
+ * lse: fp32 [B, 12, N] log-sum-exp of the scaled scores (saved for backward) or NULL.
+ *
+ * ATTENTION MAPS.  Two flag bits, ORed into `dtype` of maest_attn_fwd_rows / maest_attn_fwd, turn the call into one that writes the
+ * probabilities themselves instead of attn @ v (base codes MAEST_F32, MAEST_BF16, MAEST_BF16_QS, MAEST_F32X3; with MAEST_F32X3_A3:
+ * MAEST_ERR_INVALID):
+ *   MAEST_ATTN_PROBS                          out: fp32 [B, 12, q_rows, N], contiguous, EXACTLY q_rows rows per head (not the forward's rows
+ *                                             up to the next multiple of 32): out[b, h, q, k] = softmax_k(scale * q_{b,h,q} . k_{b,h,k}) for
+ *                                             the first q_rows queries of every clip against all N keys.
+ *   MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN  out: fp32 [B, q_rows, N], the mean over the heads, defined as
+ *                                             (((p_0 + p_1) + p_2) + ... + p_11) * fp32(1 / 12) in fp32, heads ascending, p_h the values the
+ *                                             per-head form writes: one writer per element, no atomics, bit-reproducible.
+ * The kernel is self-contained: it forms every row's maximum and sum (of the unrounded exponentials, fp32) in a first pass over the keys
+ * and writes 2^(t - m) / l in a second; it reads no lse of another kernel, and `lse` must be NULL (MAEST_ERR_INVALID otherwise).  qkv and
+ * out 16-byte aligned, q_rows in 1..N as ever.  Under MAEST_BF16_QS the q columns hold q' and the exponent factor is 1. */
+#define MAEST_ATTN_PROBS 0x100
+#define MAEST_ATTN_PROBS_MEAN 0x200
 int maest_attn_fwd(const void* qkv, void* out, float* lse, int B, int N, int dtype, float scale,
                    void* stream);
 /* delta: fp32 [B,12,N] workspace (rowsum(dO*O)); dqkv: [B*N, 2304] same layout as qkv.

@@ -22,6 +22,7 @@ F16 = 3     # IEEE half, input of maest_patch_im2col only (and dx of maest_patch
 BF16_QS = 4 # bf16 qkv tensor with q columns pre-multiplied by scale * log2(e) (maest_attn_* dtype only)
 SPLIT3_A, SPLIT3_B, F32X3_A3 = 5, 6, 7   # the split-bf16 product as one bf16 GEMM of 3 K (include/maest_hip.h)
 F32X3 = 2   # fp32 tensors, split-bf16 matrix products (maest_gemm_nt in_dtype / maest_attn_fwd dtype only)
+ATTN_PROBS, ATTN_PROBS_MEAN = 0x100, 0x200   # flag bits ORed into the dtype of maest_attn_fwd(_rows): the attention maps (include/maest_hip.h)
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_MUL, EPI_ATOMIC = 0, 1, 2, 3, 4
 
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float

@@ -20,7 +20,8 @@
 // so the probability tile never leaves registers and no cross-lane shuffles are needed beyond one
 // half-wave exchange for the running max.  Scores are never written to HBM; the only saved
 // statistic is the per-row log-sum-exp.  N is ragged (560, 290, 281, 875, 1685 ...): tail keys are
-// masked, tail rows are zero-filled in LDS and never stored.
+// masked, tail rows are zero-filled in LDS and never stored.  (The one kernel that does write probabilities is attn_probs_kernel, the
+// attention maps of MAEST_ATTN_PROBS: an output of its own, read by no other kernel.)
 //
 // One template serves both numeric modes: T = bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate,
 // fp32 softmax) and T = float (v_mfma_f32_32x32x2_f32, exact fp32 -- parity mode).
@@ -348,6 +349,156 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
             store_dT_ok<T>(o, out + ((int64_t)b * N + q) * OUT_LD + head * HD, lane, inv, ok);
         }
         if (ok && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
+    }
+}
+
+// =================================================================================== attention maps
+// MAEST_ATTN_PROBS: the probabilities themselves, out[b, head, q, k] = softmax_k(scale q k^T) in fp32 for the first q_rows queries of every clip
+// (exactly q_rows rows per head), or with MAEST_ATTN_PROBS_MEAN their mean over the heads, out[b, q, k].  The forward above never holds a
+// normalised row (its P lives tile by tile in registers, against a running maximum), so this kernel makes TWO passes over the keys of a
+// (clip, head, 128-query block): pass 1 is the forward's online maximum / sum (the sum of the unrounded exponentials, fp32), pass 2 forms
+// the same scores again -- the same MFMA sequence on the same operands: bit-equal -- and writes 2^(t - m) / l.  Nothing is read from another
+// kernel's lse (the forward forms round differently; a map must sum to 1 by its own arithmetic).
+// The N^2 write is this kernel's time.  In the S^T accumulator a lane holds 16 keys of ONE query: stored from registers that would be
+// 16-byte pieces of 64 different rows per instruction.  Each wave therefore turns its [64 keys][32 queries] tile through LDS (four float4
+// per lane and key block) and stores it a query row at a time: one dword per lane, 64 consecutive keys = 256 contiguous bytes per wave
+// instruction, the full-rate store shape at any row alignment (N need not be a multiple of 4: rows start on 4-byte boundaries only).
+// MEAN: one workgroup owns the output rows of its (clip, query block) and walks the heads in ascending order, head h adding its
+// probabilities to what heads 0 .. h - 1 left in `out` (plain loads and stores of elements this very lane wrote; head 0 stores, head 11
+// scales by fp32(1 / 12)): (((p0 + p1) + p2) + ... + p11) * fp32(1 / 12) with one writer per element, bit-reproducible.
+constexpr int PROBS_PITCH = 64 * 4 + 16;          // bytes of one query row of a wave's [32 queries][64 keys] fp32 staging tile
+constexpr int PROBS_STAGE = 4 * 32 * PROBS_PITCH; // four waves
+
+// S^T[key][q] of one 64-key tile, keys past N at NEG_BIG (the ragged last tile)
+template <typename T, bool X3>
+__device__ __forceinline__ void probs_scores(f32x16_t (&s)[2], const char* k_lds, int lane, const chunk16 (&qf)[AttnCfg<T>::STEPS],
+                                             int key0, int N) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
+        mma_rows<T, X3>(s[kb], k_lds, kb * 32, lane, qf);
+    }
+    if (key0 + 64 > N) {
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                if (key0 + kb * 32 + frag_row(r, lane) >= N) s[kb][r] = NEG_BIG;
+    }
+}
+
+template <typename T, bool X3, bool MEAN>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_probs_kernel(const T* __restrict__ qkv, float* __restrict__ out,
+                                                                                  int B, int N, float sc_c2, int q_rows) {
+    using C = AttnCfg<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x K[key][d], then per wave P[32 queries][64 keys]
+    constexpr int NH = MEAN ? NHEADS : 1;                         // heads this workgroup walks
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+    const int nrb = (q_rows + 127) / 128;
+    int rb, head0, b;
+    if constexpr (MEAN) {
+        const int w = xcd_remap(blockIdx.x, nrb * B);
+        rb = w % nrb; head0 = 0; b = w / nrb;
+    } else {
+        const AttnBlock blk = attn_block(nrb, B);
+        rb = blk.rb; head0 = blk.head; b = blk.b;
+    }
+    const int q0 = rb * 128 + wave * 32;
+    const int q = q0 + (lane & 31);
+    const bool wave_active = q0 < q_rows;                         // wave-uniform; the other waves only help staging the K tiles
+    const int nr = q_rows - q0 < 32 ? q_rows - q0 : 32;           // rows of this wave that exist in `out`
+    const T* qbase = qkv + (int64_t)b * N * QKV_LD + head0 * HD;
+    const T* kbase = qbase + NHEADS * HD;
+    float* orow = out + ((MEAN ? (int64_t)b : (int64_t)b * NHEADS + head0) * q_rows + q0) * N;   // row q0 of this workgroup's map
+    char* stage = smem + 2 * C::TILE + wave * 32 * PROBS_PITCH;
+
+    const int ntiles = (N + 63) / 64;
+    const int nsteps = NH * 2 * ntiles;                           // (head, pass, key tile), K tiles double-buffered across all of them
+    const float c2 = sc_c2;
+    chunk16 qf[C::STEPS];
+    TileRegs<T> kr;
+    tile_load<T>(kr, kbase, QKV_LD, 0, N, tid);
+    tile_store_rows<T>(kr, smem, tid);
+    __syncthreads();
+    float m_run = NEG_BIG, l_run = 0.0f, inv = 0.0f;
+    int hh = 0, pass = 0, kt = 0;
+    for (int it = 0; it < nsteps; ++it) {
+        const char* k_lds = smem + (it & 1) * C::TILE;
+        // the step after this one
+        int hh_n = hh, pass_n = pass, kt_n = kt + 1;
+        if (kt_n == ntiles) {
+            kt_n = 0;
+            if (++pass_n == 2) { pass_n = 0; ++hh_n; }
+        }
+        const bool more = it + 1 < nsteps;
+        if (more) tile_load<T>(kr, kbase + hh_n * HD, QKV_LD, kt_n * 64, N, tid);
+        if (wave_active) {
+            if (pass == 0 && kt == 0) {
+                row_frags_load<T>(qf, qbase + hh * HD, QKV_LD, q, N, h);
+                m_run = NEG_BIG;
+                l_run = 0.0f;
+            }
+            f32x16_t s[2];
+            probs_scores<T, X3>(s, k_lds, lane, qf, kt * 64, N);
+            if (pass == 0) {
+                // the forward's online softmax in the scaled log2 domain (attn_fwd_kernel), statistics only
+                float mx = NEG_BIG;
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
+                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+                const float m_new = fmaxf(m_run, mx * c2);
+                const float alpha = fast_exp2<T>(m_run - m_new);
+                m_run = m_new;
+                const f32x2_t c2v = {c2, c2}, nm = {-m_new, -m_new};
+                f32x2_t ps = {0.0f, 0.0f};
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2_t sv = {s[kb][r], s[kb][r + 1]};
+                        const f32x2_t e = __builtin_elementwise_fma(sv, c2v, nm);
+                        const f32x2_t pv = {fast_exp2<T>(e[0]), fast_exp2<T>(e[1])};
+                        ps += pv;
+                    }
+                l_run = l_run * alpha + (ps[0] + ps[1]);          // per half-wave partial; the halves meet below
+                if (kt == ntiles - 1) inv = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
+            } else {
+                // p = 2^(t - m) / l against the row's final maximum, into this wave's staging tile as P[query][key]
+                const f32x2_t c2v = {c2, c2}, nm = {-m_run, -m_run};
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x2_t s0 = {s[kb][4 * g], s[kb][4 * g + 1]}, s1 = {s[kb][4 * g + 2], s[kb][4 * g + 3]};
+                        const f32x2_t e0 = __builtin_elementwise_fma(s0, c2v, nm), e1 = __builtin_elementwise_fma(s1, c2v, nm);
+                        // (registers 4 g .. 4 g + 3 are keys 32 kb + 8 g + 4 h + 0 .. 3: frag_row)
+                        *reinterpret_cast<float4*>(stage + (lane & 31) * PROBS_PITCH + (kb * 32 + 8 * g + 4 * h) * 4) =
+                            make_float4(fast_exp2<T>(e0[0]) * inv, fast_exp2<T>(e0[1]) * inv, fast_exp2<T>(e1[0]) * inv, fast_exp2<T>(e1[1]) * inv);
+                    }
+            }
+        }
+        if (more) tile_store_rows<T>(kr, smem + ((it + 1) & 1) * C::TILE, tid);
+        __syncthreads();
+        if (wave_active && pass == 1) {
+            const int key = kt * 64 + lane;
+            if (key < N) {
+                const float* sp = reinterpret_cast<const float*>(stage + lane * 4);
+                float* op = orow + key;
+                for (int r = 0; r < nr; ++r) {
+                    float v = sp[r * (PROBS_PITCH / 4)];
+                    if constexpr (MEAN) {
+                        if (hh > 0) v = op[(int64_t)r * N] + v;
+                        if (hh == NHEADS - 1) v = v * (1.0f / 12.0f);
+                    }
+                    op[(int64_t)r * N] = v;
+                }
+            }
+        }
+        hh = hh_n; pass = pass_n; kt = kt_n;
     }
 }
 
@@ -1711,6 +1862,24 @@ static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N,
 }
 
 template <typename T, bool X3 = false>
+static int attn_probs_launch(const void* qkv, void* out, int B, int N, AttnScale sc, int q_rows, bool mean, hipStream_t st) {
+    using C = AttnCfg<T>;
+    const int smem_bytes = 2 * C::TILE + PROBS_STAGE;
+    const int nrb = (q_rows + 127) / 128;
+    if (mean) {
+        static DeviceOnce once_m;
+        ensure_dynamic_lds(once_m, &attn_probs_kernel<T, X3, true>, smem_bytes);
+        hipLaunchKernelGGL((attn_probs_kernel<T, X3, true>), dim3(nrb * B), dim3(256), smem_bytes, st, (const T*)qkv, (float*)out, B, N, sc.c2, q_rows);
+    } else {
+        static DeviceOnce once;
+        ensure_dynamic_lds(once, &attn_probs_kernel<T, X3, false>, smem_bytes);
+        hipLaunchKernelGGL((attn_probs_kernel<T, X3, false>), dim3(nrb * NHEADS * B), dim3(256), smem_bytes, st, (const T*)qkv, (float*)out, B, N, sc.c2,
+                           q_rows);
+    }
+    return check_launch("maest_attn_fwd(probabilities)");
+}
+
+template <typename T, bool X3 = false>
 static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int B, int N, AttnScale sc, int q_rows, hipStream_t st) {
     using C = AttnCfg<T>;
@@ -1791,6 +1960,20 @@ extern "C" int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B
     MAEST_REQUIRE(qkv && out, "maest_attn_fwd: null pointer");
     MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_fwd: bad shape B=%d N=%d", B, N);
     MAEST_REQUIRE(q_rows > 0 && q_rows <= N, "maest_attn_fwd_rows: q_rows = %d outside 1..N", q_rows);
+    if (dtype & (MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN)) {     // the attention maps: `out` is fp32 [B, 12, q_rows, N] / [B, q_rows, N]
+        const int base = dtype & ~(MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN);
+        MAEST_REQUIRE(dtype & MAEST_ATTN_PROBS, "maest_attn_fwd: MAEST_ATTN_PROBS_MEAN without MAEST_ATTN_PROBS (dtype %d)", dtype);
+        MAEST_REQUIRE(base != MAEST_F32X3_A3, "maest_attn_fwd: MAEST_ATTN_PROBS writes fp32 probabilities: no MAEST_F32X3_A3 form");
+        MAEST_REQUIRE(base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS,
+                      "maest_attn_fwd: bad dtype %d under MAEST_ATTN_PROBS", base);
+        MAEST_REQUIRE(lse == nullptr, "maest_attn_fwd: MAEST_ATTN_PROBS saves no lse: pass NULL");
+        MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "maest_attn_fwd: 16-byte alignment");
+        const AttnScale scp = attn_scale(scale, base == MAEST_BF16_QS);
+        const bool mean = (dtype & MAEST_ATTN_PROBS_MEAN) != 0;
+        if (base == MAEST_F32X3) return attn_probs_launch<float, true>(qkv, out, B, N, scp, q_rows, mean, (hipStream_t)stream);
+        return base == MAEST_F32 ? attn_probs_launch<float>(qkv, out, B, N, scp, q_rows, mean, (hipStream_t)stream)
+                                 : attn_probs_launch<bf16_t>(qkv, out, B, N, scp, q_rows, mean, (hipStream_t)stream);
+    }
     MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16 || dtype == MAEST_F32X3 || dtype == MAEST_BF16_QS || dtype == MAEST_F32X3_A3,
                   "maest_attn_fwd: bad dtype %d", dtype);
     MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "maest_attn_fwd: 16-byte alignment");

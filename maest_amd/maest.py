@@ -404,9 +404,11 @@ class _Engine:
             return self._forward(*args, **kw)
 
     def _forward(self, x3: torch.Tensor, dt, *, toffset: int, tok_ft: torch.Tensor, perm, lam, stripes=None,
-                 stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False):
+                 stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, maps=None):
         """x3: fp32 [B, F, T] on the device; tok_ft: int32 [P, 2] kept patch tokens.  Returns (outputs, ctx).
-        x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3")."""
+        x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3").
+        maps (MAEST.attention_maps) = (out, blocks, q_rows, head_mean): for every block index in `blocks`, out[index] = the attention
+        probabilities of that block's qkv (ops.attn_probs); None: exactly the launches below."""
         m, W = self.m, (self.w_f16 if f16 else self.w)
         if x3m is None:
             x3m = m.precision == "bf16x3"
@@ -514,6 +516,8 @@ class _Engine:
                 qkv = ops.gemm_nt(ln1, w3[(i, "qkv")], qkv_bias[i], out_dtype=torch.float32, split3=True)
             else:
                 qkv = gemm_nt(ln1, W.get(blk.attn.qkv.weight, dt), qkv_bias[i], out_dtype=dt)
+            if maps is not None and i in maps[1]:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
+                maps[0][i] = ops.attn_probs(qkv, B, N, scale, q_rows=maps[2], x3=x3m, q_prescaled=qs, head_mean=maps[3])
             tail = self.head_tail and stop_block < 0 and i == nblocks - 1
             # (training needs the backward kernel that honours the restriction; otherwise the attention stays complete
             # and only the per-token part of the block is restricted)
@@ -1261,6 +1265,14 @@ class MAEST(nn.Module):
         ``_mixup=(perm, lam)``, ``_specmask=(t_stripes, f_stripes)`` and ``_patchout=(toffset, kept_time_columns)``
         are private hooks used by ``maest_amd.module.Module.training_step`` (mixup and SpecMasking fused into the
         patch-embedding operand load) and by the parity tests (pinned draws)."""
+        x3, dt, kw, need_grad, _ = self._resolve_call(x, melspectrogram_input, _mixup, _patchout, _specmask)
+        return self._run(x3, dt, kw, need_grad, transformer_block, return_self_attention,
+                         plain=_mixup is None and _patchout is None and _specmask is None)
+
+    def _resolve_call(self, x, melspectrogram_input, _mixup, _patchout, _specmask, recording=None):
+        """What a forward call resolves before it launches anything: the rank dispatch, the shape checks, the numeric mode, the kept
+        tokens and the private hooks -> (x3 [B, F, T] on the device, compute dtype, the engine's keyword arguments, whether a graph is
+        recorded, (F', T') of the patch grid).  recording=False (attention_maps): never record, whatever grad mode says."""
         x = self._prepare_input(x, melspectrogram_input)
         if x.dim() != 4 or x.shape[1] != 1:
             raise Exception(f"expected input of shape [B, 1, F, T], got {tuple(x.shape)}")
@@ -1283,7 +1295,8 @@ class MAEST(nn.Module):
         x3 = x3.contiguous()
         # a graph is recorded when grad mode is on and a parameter or the input requires grad -- for the full forward and for the
         # embedding of block k alike (the reference's forward_features is ordinary autograd, models/maest.py:808-829)
-        need_grad = torch.is_grad_enabled() and (x3.requires_grad or any(p.requires_grad for p in self.parameters()))
+        need_grad = (recording is not False and torch.is_grad_enabled()
+                     and (x3.requires_grad or any(p.requires_grad for p in self.parameters())))
         if need_grad and not self.training and self.precision in ("fp16", "float16", "half"):
             need_grad = False     # precision="fp16": eval() forwards record no graph even outside no_grad (a backward through them fails loudly
                                   # on outputs that do not require grad); a train() forward records in half and wants a scaled loss (_resolve_precision)
@@ -1319,7 +1332,10 @@ class MAEST(nn.Module):
         kw = dict(toffset=int(toffset), tok_ft=tok_ft, perm=perm, lam=lam, stripes=stripes, x3m=mode == "bf16x3")
         if mode == "fp16":
             kw["f16"] = True
+        return x3, dt, kw, need_grad, (Fp, Tp)
 
+    def _run(self, x3, dt, kw, need_grad, transformer_block, return_self_attention, plain):
+        """The launches of a resolved forward call.  plain: no private hook is set (the HIP-graph replay serves such calls only)."""
         if need_grad and self._param_names is None:
             named = list(self.named_parameters())
             self._param_names = [n for n, _ in named]
@@ -1337,8 +1353,7 @@ class MAEST(nn.Module):
             outs = _MaestFn.apply(self, x3, dt, kw, self._param_names, *self._param_list)
         else:
             with torch.no_grad():
-                if (self.hip_graph and x3.is_cuda and not self.training and _mixup is None and _patchout is None
-                        and _specmask is None):
+                if self.hip_graph and x3.is_cuda and not self.training and plain:
                     outs = self._graph_forward(x3, dt, kw)
                 else:
                     outs = self._eval_forward(x3, dt, kw)
@@ -1488,6 +1503,69 @@ class MAEST(nn.Module):
             logits = self.forward(x)[0]
         activations = ops.sigmoid_mean(logits.detach().contiguous())
         return activations.cpu().numpy(), self.labels
+
+    def attention_maps(self, x, blocks=None, queries: str = "head", heads: str = "all", melspectrogram_input: bool = False, *,
+                       _patchout=None) -> "AttentionMaps":
+        """The attention probabilities softmax(q k^T * scale) of the reference's Attention.forward (models/maest.py:371-372), per block
+        -- what the HF-AST layout calls output_attentions --, next to the outputs of the same forward.
+
+        x: everything ``forward`` accepts (1-D / 2-D audio, 2-D / 3-D / 4-D mel: the same rank dispatch, chunking and exceptions).
+        blocks: an int, an iterable of ints or None (all); negative indices count from the end.  queries: "head" -- the rows of the cls
+        and the dist token, [.., 2, N] -- or "all", [.., N, N].  heads: "all" -- [B, 12, Q, N] -- or "mean" -- [B, Q, N], the mean over
+        the heads.  One forward under no_grad in the model's current mode and precision (eval(): the evaluation kernels, "auto" = bf16x3;
+        train(): the patchout draws apply and ``tokens`` says which patches were kept), run eagerly to its end on the caller's stream
+        (no two-stream split, no HIP-graph replay; the weights' operand copies are the ones every forward shares); in every requested
+        block one more launch writes the map from the qkv tensor the block computed anyway (ops.attn_probs).  The maps are detached
+        fp32 tensors.  `return_self_attention=True` of ``forward`` is a different tensor: proj(attn @ v) of one block, pooled."""
+        if queries not in ("head", "all"):
+            raise ValueError(f"queries must be 'head' or 'all', got {queries!r}")
+        if heads not in ("all", "mean"):
+            raise ValueError(f"heads must be 'all' or 'mean', got {heads!r}")
+        depth = len(self.blocks)
+        if blocks is None:
+            want = list(range(depth))
+        else:
+            if isinstance(blocks, (bool, str)) or not (isinstance(blocks, int) or hasattr(blocks, "__iter__")):
+                raise TypeError(f"blocks must be an int, an iterable of ints or None, got {blocks!r}")
+            want = [blocks] if isinstance(blocks, int) else list(blocks)
+            for i in want:
+                if isinstance(i, bool) or not isinstance(i, int):
+                    raise TypeError(f"blocks must be an int, an iterable of ints or None, got an element {i!r}")
+                if not -depth <= i < depth:
+                    raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
+            want = [i % depth for i in want]
+        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
+        maps = {}
+        with torch.no_grad():
+            outs, _ = self._engine.forward(x3, dt, maps=(maps, frozenset(want), HEAD_TOKENS if queries == "head" else None, heads == "mean"), **kw)
+        return AttentionMaps(outs[0], outs[-1], {i: maps[i] for i in sorted(maps)}, kw["tok_ft"], grid,
+                             logits_dist=outs[1] if len(outs) == 3 else None)
+
+
+class AttentionMaps:
+    """What MAEST.attention_maps returns.  logits, features: the outputs of the same forward (logits_dist: the distillation head's, with
+    distilled_type="separated"; else None).  maps: {block index: fp32 [B, 12, Q, N] or, heads="mean", [B, Q, N]}; key token 0 is cls, 1 is
+    dist, tokens[j] = (frequency patch, time patch) of key token 2 + j (int32 [N - 2, 2]: the patches the forward kept, in sequence
+    order); grid = (F', T') of the complete patch grid."""
+
+    def __init__(self, logits, features, maps, tokens, grid, logits_dist=None):
+        self.logits, self.features, self.maps, self.tokens, self.grid, self.logits_dist = logits, features, maps, tokens, tuple(grid), logits_dist
+
+    def to_grid(self, block: int, query: int = 0, head: Optional[int] = None) -> torch.Tensor:
+        """Row `query` of block `block`'s map (0: cls, 1: dist) laid out on the patch grid: [B, F', T'] for one head (or a map of
+        heads="mean"), [B, 12, F', T'] for every head (head=None); NaN where the forward dropped the patch."""
+        p = self.maps[block]
+        if p.dim() == 4:
+            row = p[:, :, query, 2:] if head is None else p[:, head, query, 2:]
+        else:
+            if head is not None:
+                raise ValueError("these maps are the mean over the heads: there is no head to select")
+            row = p[:, query, 2:]
+        Fp, Tp = self.grid
+        tok = self.tokens.to(device=row.device, dtype=torch.long)
+        out = torch.full(row.shape[:-1] + (Fp * Tp,), float("nan"), dtype=row.dtype, device=row.device)
+        out[..., tok[:, 0] * Tp + tok[:, 1]] = row
+        return out.reshape(row.shape[:-1] + (Fp, Tp))
 
 
 # --------------------------------------------------------------------------------------

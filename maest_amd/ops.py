@@ -398,6 +398,22 @@ def attn_fwd(qkv: torch.Tensor, B: int, N: int, scale: float, save_lse=False, q_
     return (out, lse) if save_lse else out
 
 
+def attn_probs(qkv: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False, q_prescaled=False, head_mean=False) -> torch.Tensor:
+    """The attention maps of a qkv tensor: fp32 softmax(scale q k^T) of the first q_rows queries of every clip (None: all N) against all N
+    keys, [B, 12, q_rows, N] -- or, head_mean, their mean over the heads, [B, q_rows, N] = (((p0 + p1) + ...) + p11) * fp32(1 / 12).
+    MAEST_ATTN_PROBS (| MAEST_ATTN_PROBS_MEAN) on maest_attn_fwd_rows; x3 / q_prescaled as in attn_fwd."""
+    _chk(qkv)
+    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    assert qkv.shape == (B * N, 3 * EMBED)
+    q_rows = N if q_rows is None else q_rows
+    out = torch.empty((B, q_rows, N) if head_mean else (B, HEADS, q_rows, N), dtype=torch.float32, device=qkv.device)
+    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_PROBS | (_lib.ATTN_PROBS_MEAN if head_mean else 0)
+    # (work: the score product, formed twice)
+    _timed_call("maest_attn_probs", _attn_flops(B, N, q_rows, 4.0), _p(qkv), _p(out), None, B, N, code, scale, q_rows, _s(qkv),
+                _entry="maest_attn_fwd_rows")
+    return out
+
+
 def attn_bwd_rows_supported(dtype, N: int) -> bool:
     """Whether maest_attn_bwd_rows serves q_rows < N for this shape (the fused bf16 kernel: include/maest_hip.h)."""
     return dtype == torch.bfloat16 and -(-N // 32) + 2 <= 12 and get_option("attn_bwd") in (0, 3)
