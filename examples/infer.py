@@ -32,6 +32,7 @@ def main():
         _, emb7 = model(audio, transformer_block=6)             # cls + dist + mean token of block 6
         activations, labels = model.predict_labels(audio)
         maps = model.attention_maps(audio, blocks=-1, heads="mean")     # softmax(q k^T * scale) of the last block, cls / dist rows
+        roll = model.attention_rollout(audio)                   # which patches feed cls / dist through all 12 blocks
     top = np.argsort(activations)[::-1][:5]
     print("logits", tuple(logits.shape), "embeddings", tuple(embeddings.shape), "block-6 embedding", tuple(emb7.shape))
     for i in top:
@@ -42,6 +43,9 @@ def main():
     best = torch.topk(per_t, 5).indices.tolist()
     print(f"block {last} cls attention, top time patches of chunk 0 (of {maps.grid[1]}; 0.16 s apart):",
           ", ".join(f"t={t} ({per_t[t].item():.4f})" for t in best))
+    per_t = torch.nan_to_num(roll.to_grid(row=0)[0]).sum(0)
+    best = torch.topk(per_t, 5).indices.tolist()
+    print("cls attention rollout over all blocks, top time patches of chunk 0:", ", ".join(f"t={t} ({per_t[t].item():.4f})" for t in best))
 
 
 if __name__ == "__main__":

@@ -304,6 +304,22 @@ int maest_attn_bwd(const void* qkv, const void* out, const void* dout, const flo
  * [q_rows, roundup(q_rows, 32)) must be zero, later rows are not read (nor are out / lse there); dK, dV complete, dQ = 0
  * for every query >= q_rows.  q_rows = N is maest_attn_fwd / maest_attn_bwd.  Backward with q_rows < N is served by
  * the fused bf16 kernel only (N <= 320): MAEST_ERR_INVALID otherwise. */
+/* WEIGHTED ATTENTION POOLING (the step of attention rollout).  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_ROWS(R), ORed into `dtype` of
+ * maest_attn_bwd_rows / maest_attn_bwd (base codes those of MAEST_ATTN_PROBS: MAEST_F32, MAEST_F32X3, MAEST_BF16 -- the half build: IEEE
+ * half --, MAEST_BF16_QS; MAEST_F32X3_A3: MAEST_ERR_INVALID), turns the call into R <= 8 row vectors times the head-mean attention matrix,
+ * without an N x N write:
+ *   dout  = W, fp32 [B, R, N].  Only columns < q_rows are read; columns >= q_rows may hold anything (NaN included).
+ *   dqkv  = Y, fp32 [B, R, N], contiguous: the call writes exactly these elements.
+ *   delta = workspace, fp32 [B, 12, N]: rows < q_rows of each (clip, head) are written with lse2 = m + log2(l), the row statistic in the
+ *           log2 domain; nothing beyond them.
+ *   out, lse must be NULL (MAEST_ERR_INVALID otherwise): like the maps, the call normalises by its own arithmetic.
+ * With c2 as for the forward (scale * log2 e; 1 under MAEST_BF16_QS) and t_h[q, k] = c2 * q_h . k_h on the operands as stored,
+ *   Y[b, r, k] = fp32(1 / 12) * (((s_0 + s_1) + s_2) + ... + s_11),   s_h = sum_{q < q_rows} W[b, r, q] * 2^(t_h[q, k] - lse2_h[q]),
+ * heads ascending, the order of the sum over q the kernel's own but fixed, one writer per element, no atomics: two calls are bit-identical.
+ * P and W stay fp32 in this product in every mode; only q k^T takes the mode's arithmetic.  q_rows in 1..N (maest_attn_bwd: q_rows = N);
+ * qkv, dout, delta, dqkv 16-byte aligned. */
+#define MAEST_ATTN_APPLY 0x400
+#define MAEST_ATTN_APPLY_ROWS(r) (((r) - 1) << 16)     /* R = 1 .. 8 weight rows */
 int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B, int N, int dtype, float scale, int q_rows,
                         void* stream);
 int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

@@ -23,6 +23,14 @@ BF16_QS = 4 # bf16 qkv tensor with q columns pre-multiplied by scale * log2(e) (
 SPLIT3_A, SPLIT3_B, F32X3_A3 = 5, 6, 7   # the split-bf16 product as one bf16 GEMM of 3 K (include/maest_hip.h)
 F32X3 = 2   # fp32 tensors, split-bf16 matrix products (maest_gemm_nt in_dtype / maest_attn_fwd dtype only)
 ATTN_PROBS, ATTN_PROBS_MEAN = 0x100, 0x200   # flag bits ORed into the dtype of maest_attn_fwd(_rows): the attention maps (include/maest_hip.h)
+ATTN_APPLY = 0x400   # flag bit ORed into the dtype of maest_attn_bwd(_rows): weighted attention pooling (include/maest_hip.h)
+
+
+def attn_apply_rows(r: int) -> int:
+    """MAEST_ATTN_APPLY_ROWS(r): the number of weight rows, R = 1 .. 8, as bits of the dtype argument."""
+    return (r - 1) << 16
+
+
 EPI_NONE, EPI_GELU, EPI_RESIDUAL, EPI_MUL, EPI_ATOMIC = 0, 1, 2, 3, 4
 
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float

@@ -388,6 +388,33 @@ __device__ __forceinline__ void probs_scores(f32x16_t (&s)[2], const char* k_lds
     }
 }
 
+// One key tile of the forward's online softmax in the scaled log2 domain (attn_fwd_kernel), statistics only: the running maximum and
+// the running fp32 sum of the unrounded exponentials of this lane's query.  l_run is a per half-wave partial: the halves meet at the end.
+template <typename T>
+__device__ __forceinline__ void probs_stats_step(const f32x16_t (&s)[2], float c2, float& m_run, float& l_run) {
+    float mx = NEG_BIG;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx * c2);
+    const float alpha = fast_exp2<T>(m_run - m_new);
+    m_run = m_new;
+    const f32x2_t c2v = {c2, c2}, nm = {-m_new, -m_new};
+    f32x2_t ps = {0.0f, 0.0f};
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2) {
+            const f32x2_t sv = {s[kb][r], s[kb][r + 1]};
+            const f32x2_t e = __builtin_elementwise_fma(sv, c2v, nm);
+            const f32x2_t pv = {fast_exp2<T>(e[0]), fast_exp2<T>(e[1])};
+            ps += pv;
+        }
+    l_run = l_run * alpha + (ps[0] + ps[1]);
+}
+
 template <typename T, bool X3, bool MEAN>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_probs_kernel(const T* __restrict__ qkv, float* __restrict__ out,
                                                                                   int B, int N, float sc_c2, int q_rows) {
@@ -443,28 +470,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_probs_kernel
             f32x16_t s[2];
             probs_scores<T, X3>(s, k_lds, lane, qf, kt * 64, N);
             if (pass == 0) {
-                // the forward's online softmax in the scaled log2 domain (attn_fwd_kernel), statistics only
-                float mx = NEG_BIG;
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kb][r]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m_new = fmaxf(m_run, mx * c2);
-                const float alpha = fast_exp2<T>(m_run - m_new);
-                m_run = m_new;
-                const f32x2_t c2v = {c2, c2}, nm = {-m_new, -m_new};
-                f32x2_t ps = {0.0f, 0.0f};
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int r = 0; r < 16; r += 2) {
-                        const f32x2_t sv = {s[kb][r], s[kb][r + 1]};
-                        const f32x2_t e = __builtin_elementwise_fma(sv, c2v, nm);
-                        const f32x2_t pv = {fast_exp2<T>(e[0]), fast_exp2<T>(e[1])};
-                        ps += pv;
-                    }
-                l_run = l_run * alpha + (ps[0] + ps[1]);          // per half-wave partial; the halves meet below
+                probs_stats_step<T>(s, c2, m_run, l_run);
                 if (kt == ntiles - 1) inv = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
             } else {
                 // p = 2^(t - m) / l against the row's final maximum, into this wave's staging tile as P[query][key]
@@ -499,6 +505,188 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_probs_kernel
             }
         }
         hh = hh_n; pass = pass_n; kt = kt_n;
+    }
+}
+
+// =================================================================================== attention apply
+// MAEST_ATTN_APPLY: Y[b, r, k] = fp32(1 / 12) * (((s_0 + s_1) + s_2) + ... + s_11),  s_h = sum_{q < q_rows} W[b, r, q] * P_h[q, k], R <= 8 weight
+// rows times the head-mean attention matrix without ever writing a probability: the row-vector x matrix product of attention rollout.  It is
+// the dV-shaped product of the backward (lane = key, registers = queries: S = Q K^T, the K rows as per-lane fragments, the Q tiles in LDS)
+// with dO replaced by R weight columns, so the product over the queries is R fp32 FMAs per probability in the lane that owns the key and
+// needs no cross-lane step beyond one half-wave exchange per head.
+//   launch 1  attn_apply_stats_kernel: pass 1 of attn_probs_kernel per (clip, head, 128-query block) -- the online maximum and the fp32 sum
+//             of the unrounded exponentials -- stored as ONE number per row, lse2 = m + log2(l) (log2 domain), rows < q_rows only.
+//   launch 2  attn_apply_kernel: one workgroup per (clip, 128-key block), a wave per 32 keys.  It walks the heads in ascending order and, per
+//             head, the 64-query tiles below q_rows (double-buffered in LDS next to their lse2 and W columns, queries >= q_rows staged as
+//             zero rows with W = 0 and lse2 = 0: they add exact zeros, whatever W holds there); p = 2^(c2 s - lse2[q]); acc[r] = fma(W[r][q],
+//             p, acc[r]) in a fixed order.  One writer per element of Y, no atomics: bit-reproducible.
+// P and W stay fp32; only Q K^T takes the mode's arithmetic (T, X3).  RP: the weight rows the kernel carries (R rounded up to 2, 4 or 8).
+template <typename T, bool X3>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_stats_kernel(const T* __restrict__ qkv, float* __restrict__ lse2,
+                                                                                        int B, int N, float sc_c2, int q_rows) {
+    using C = AttnCfg<T>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x K[key][d]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+    const AttnBlock blk = attn_block((q_rows + 127) / 128, B);
+    const int q0 = blk.rb * 128 + wave * 32;
+    const int q = q0 + (lane & 31);
+    const bool wave_active = q0 < q_rows;                         // wave-uniform; the other waves only help staging the K tiles
+    const T* qbase = qkv + (int64_t)blk.b * N * QKV_LD + blk.head * HD;
+    const T* kbase = qbase + NHEADS * HD;
+
+    const int ntiles = (N + 63) / 64;
+    const float c2 = sc_c2;
+    chunk16 qf[C::STEPS];
+    row_frags_load<T>(qf, qbase, QKV_LD, q, N, h);
+    TileRegs<T> kr;
+    tile_load<T>(kr, kbase, QKV_LD, 0, N, tid);
+    tile_store_rows<T>(kr, smem, tid);
+    __syncthreads();
+    float m_run = NEG_BIG, l_run = 0.0f;
+    for (int kt = 0; kt < ntiles; ++kt) {
+        const char* k_lds = smem + (kt & 1) * C::TILE;
+        const bool more = kt + 1 < ntiles;
+        if (more) tile_load<T>(kr, kbase, QKV_LD, (kt + 1) * 64, N, tid);
+        if (wave_active) {
+            f32x16_t s[2];
+            probs_scores<T, X3>(s, k_lds, lane, qf, kt * 64, N);
+            probs_stats_step<T>(s, c2, m_run, l_run);
+        }
+        if (more) tile_store_rows<T>(kr, smem + ((kt + 1) & 1) * C::TILE, tid);
+        __syncthreads();
+    }
+    if (wave_active) {
+        const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+        // one rounding, once per row: an fp32 log2 and an fp32 add of a number of magnitude 8 .. 16 leave a common bias of a fraction of
+        // 2^-20 in every probability of the row, which no later division takes out
+        if (h == 0 && q < q_rows) lse2[((int64_t)blk.b * NHEADS + blk.head) * N + q] = (float)((double)m_run + log2((double)l_tot));
+    }
+}
+
+// the fp32 columns that travel with a 64-query tile: rows 0 .. RP - 1 = W[r][q], row RP = lse2[q]; zero for q >= q_rows and r >= R
+template <int RP>
+struct ApplySide {
+    static constexpr int FLOATS = (RP + 1) * 64;
+    static constexpr int PER_THREAD = (FLOATS + 255) / 256;
+    float v[PER_THREAD];
+};
+template <int RP>
+__device__ __forceinline__ void apply_side_load(ApplySide<RP>& sd, const float* __restrict__ w_clip, const float* __restrict__ lse2_head, int N,
+                                                int R, int q0, int q_rows, int tid) {
+#pragma unroll
+    for (int i = 0; i < ApplySide<RP>::PER_THREAD; ++i) {
+        const int idx = tid + i * 256, row = idx >> 6, q = q0 + (idx & 63);
+        float x = 0.0f;
+        if (idx < ApplySide<RP>::FLOATS && q < q_rows) {
+            if (row == RP) x = lse2_head[q];
+            else if (row < R) x = w_clip[(int64_t)row * N + q];
+        }
+        sd.v[i] = x;
+    }
+}
+template <int RP>
+__device__ __forceinline__ void apply_side_store(const ApplySide<RP>& sd, char* lds, int tid) {
+#pragma unroll
+    for (int i = 0; i < ApplySide<RP>::PER_THREAD; ++i) {
+        const int idx = tid + i * 256;
+        if (idx < ApplySide<RP>::FLOATS) reinterpret_cast<float*>(lds)[idx] = sd.v[i];
+    }
+}
+
+template <typename T, bool X3, int RP>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel(const T* __restrict__ qkv, const float* __restrict__ w,
+                                                                                  const float* __restrict__ lse2, float* __restrict__ y, int B,
+                                                                                  int N, float sc_c2, int q_rows, int R) {
+    using C = AttnCfg<T>;
+    using Side = ApplySide<RP>;
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x Q[query][d], then 2 x { W[RP][64 queries], lse2[64 queries] }
+    constexpr int SIDE_BYTES = Side::FLOATS * 4;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
+    const int nkb = (N + 127) / 128;
+    const int wg = xcd_remap(blockIdx.x, nkb * B);
+    const int b = wg / nkb, key0 = (wg % nkb) * 128 + wave * 32;
+    const int key = key0 + (lane & 31);
+    const bool wave_active = key0 < N;                            // wave-uniform; the other waves only help staging the Q tiles
+    const T* qbase = qkv + (int64_t)b * N * QKV_LD;
+    const T* kbase = qbase + NHEADS * HD;
+    const float* w_clip = w + (int64_t)b * R * N;
+    const float* lse2_clip = lse2 + (int64_t)b * NHEADS * N;
+
+    const int nqt = (q_rows + 63) / 64;
+    const int nsteps = NHEADS * nqt;                              // (head, query tile), double-buffered across all of them
+    const float c2 = sc_c2;
+    chunk16 kf[C::STEPS];
+    float acc[RP], tot[RP];
+#pragma unroll
+    for (int r = 0; r < RP; ++r) { acc[r] = 0.0f; tot[r] = 0.0f; }
+    TileRegs<T> qr;
+    Side sd;
+    tile_load<T>(qr, qbase, QKV_LD, 0, q_rows, tid);              // (rows >= q_rows read as zero)
+    apply_side_load<RP>(sd, w_clip, lse2_clip, N, R, 0, q_rows, tid);
+    tile_store_rows<T>(qr, smem, tid);
+    apply_side_store<RP>(sd, smem + 2 * C::TILE, tid);
+    __syncthreads();
+    int hh = 0, qt = 0;
+    for (int it = 0; it < nsteps; ++it) {
+        const char* q_lds = smem + (it & 1) * C::TILE;
+        const float* side = reinterpret_cast<const float*>(smem + 2 * C::TILE + (it & 1) * SIDE_BYTES);
+        int hh_n = hh, qt_n = qt + 1;
+        if (qt_n == nqt) { qt_n = 0; ++hh_n; }
+        const bool more = it + 1 < nsteps;
+        if (more) {
+            tile_load<T>(qr, qbase + hh_n * HD, QKV_LD, qt_n * 64, q_rows, tid);
+            apply_side_load<RP>(sd, w_clip, lse2_clip + (int64_t)hh_n * N, N, R, qt_n * 64, q_rows, tid);
+        }
+        if (wave_active) {
+            if (qt == 0) {
+                row_frags_load<T>(kf, kbase + hh * HD, QKV_LD, key, N, h);   // (keys >= N: a clamped row, never stored)
+#pragma unroll
+                for (int r = 0; r < RP; ++r) acc[r] = 0.0f;
+            }
+#pragma unroll
+            for (int qb = 0; qb < 2; ++qb) {
+                // S[q][key] of 32 queries: registers 4 g .. 4 g + 3 are queries 32 qb + 8 g + 4 h + 0 .. 3 (frag_row)
+                f32x16_t s;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[r] = 0.0f;
+                mma_rows<T, X3>(s, q_lds, qb * 32, lane, kf);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int qo = qb * 32 + 8 * g + 4 * h;
+                    const float4 ls = *reinterpret_cast<const float4*>(side + RP * 64 + qo);
+                    const f32x2_t c2v = {c2, c2}, n0 = {-ls.x, -ls.y}, n1 = {-ls.z, -ls.w};
+                    const f32x2_t s0 = {s[4 * g], s[4 * g + 1]}, s1 = {s[4 * g + 2], s[4 * g + 3]};
+                    const f32x2_t e0 = __builtin_elementwise_fma(s0, c2v, n0), e1 = __builtin_elementwise_fma(s1, c2v, n1);
+                    const float p0 = fast_exp2<T>(e0[0]), p1 = fast_exp2<T>(e0[1]), p2 = fast_exp2<T>(e1[0]), p3 = fast_exp2<T>(e1[1]);
+#pragma unroll
+                    for (int r = 0; r < RP; ++r) {
+                        const float4 wv = *reinterpret_cast<const float4*>(side + r * 64 + qo);
+                        acc[r] = fmaf(wv.w, p3, fmaf(wv.z, p2, fmaf(wv.y, p1, fmaf(wv.x, p0, acc[r]))));
+                    }
+                }
+            }
+            if (qt == nqt - 1) {
+                // the two half-waves hold the halves of this head's sum over the queries; heads in ascending order
+#pragma unroll
+                for (int r = 0; r < RP; ++r) {
+                    const float sh = acc[r] + __shfl_xor(acc[r], 32, 64);
+                    tot[r] = hh == 0 ? sh : tot[r] + sh;
+                }
+            }
+        }
+        if (more) {
+            tile_store_rows<T>(qr, smem + ((it + 1) & 1) * C::TILE, tid);
+            apply_side_store<RP>(sd, smem + 2 * C::TILE + ((it + 1) & 1) * SIDE_BYTES, tid);
+        }
+        __syncthreads();
+        hh = hh_n; qt = qt_n;
+    }
+    if (wave_active && h == 0 && key < N) {
+#pragma unroll
+        for (int r = 0; r < RP; ++r)
+            if (r < R) y[((int64_t)b * R + r) * N + key] = tot[r] * (1.0f / 12.0f);
     }
 }
 
@@ -1879,6 +2067,32 @@ static int attn_probs_launch(const void* qkv, void* out, int B, int N, AttnScale
     return check_launch("maest_attn_fwd(probabilities)");
 }
 
+template <typename T, bool X3, int RP>
+static void attn_apply_launch_rows(const void* qkv, const float* w, const float* lse2, float* y, int B, int N, float c2, int q_rows, int R,
+                                   hipStream_t st) {
+    using C = AttnCfg<T>;
+    const int smem_bytes = 2 * C::TILE + 2 * ApplySide<RP>::FLOATS * 4;
+    static DeviceOnce once;
+    ensure_dynamic_lds(once, &attn_apply_kernel<T, X3, RP>, smem_bytes);
+    hipLaunchKernelGGL((attn_apply_kernel<T, X3, RP>), dim3(((N + 127) / 128) * B), dim3(256), smem_bytes, st, (const T*)qkv, w, lse2, y, B, N, c2,
+                       q_rows, R);
+}
+
+// MAEST_ATTN_APPLY: w fp32 [B, R, N], lse2 fp32 [B, 12, N] (workspace: written by the first launch, read by the second), y fp32 [B, R, N]
+template <typename T, bool X3 = false>
+static int attn_apply_launch(const void* qkv, const float* w, float* lse2, float* y, int B, int N, AttnScale sc, int q_rows, int R,
+                             hipStream_t st) {
+    using C = AttnCfg<T>;
+    static DeviceOnce once;
+    ensure_dynamic_lds(once, &attn_apply_stats_kernel<T, X3>, 2 * C::TILE);
+    hipLaunchKernelGGL((attn_apply_stats_kernel<T, X3>), dim3(((q_rows + 127) / 128) * NHEADS * B), dim3(256), 2 * C::TILE, st, (const T*)qkv, lse2,
+                       B, N, sc.c2, q_rows);
+    if (R <= 2) attn_apply_launch_rows<T, X3, 2>(qkv, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    else if (R <= 4) attn_apply_launch_rows<T, X3, 4>(qkv, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    else attn_apply_launch_rows<T, X3, 8>(qkv, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    return check_launch("maest_attn_bwd(apply)");
+}
+
 template <typename T, bool X3 = false>
 static int attn_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int B, int N, AttnScale sc, int q_rows, hipStream_t st) {
@@ -1993,6 +2207,26 @@ extern "C" int maest_attn_fwd(const void* qkv, void* out, float* lse, int B, int
 extern "C" int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse,
                                    float* delta, void* dqkv, int B, int N, int dtype, float scale, int q_rows,
                                    void* stream) {
+    if (dtype & MAEST_ATTN_APPLY) {     // weighted attention pooling: dout = W, dqkv = Y (fp32 [B, R, N] both), delta = the lse2 workspace
+        const int base = dtype & 0xFF, rows = ((dtype >> 16) & 0xFF) + 1;
+        MAEST_REQUIRE(qkv && dout && delta && dqkv, "maest_attn_bwd: null pointer");
+        MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_bwd: bad shape B=%d N=%d", B, N);
+        MAEST_REQUIRE(q_rows > 0 && q_rows <= N, "maest_attn_bwd_rows: q_rows = %d outside 1..N", q_rows);
+        MAEST_REQUIRE(out == nullptr && lse == nullptr, "maest_attn_bwd: MAEST_ATTN_APPLY reads no out and no lse: pass NULL");
+        MAEST_REQUIRE(base != MAEST_F32X3_A3, "maest_attn_bwd: MAEST_ATTN_APPLY keeps fp32 probabilities: no MAEST_F32X3_A3 form");
+        MAEST_REQUIRE((dtype & ~(0xFF | MAEST_ATTN_APPLY | 0xFF0000)) == 0 &&
+                          (base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS),
+                      "maest_attn_bwd: bad dtype %d under MAEST_ATTN_APPLY", dtype & ~(MAEST_ATTN_APPLY | 0xFF0000));
+        MAEST_REQUIRE(rows <= 8, "maest_attn_bwd: MAEST_ATTN_APPLY_ROWS: %d weight rows outside 1..8", rows);
+        MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)delta % 16) == 0 && ((uintptr_t)dqkv % 16) == 0,
+                      "maest_attn_bwd: 16-byte alignment");
+        const AttnScale sca = attn_scale(scale, base == MAEST_BF16_QS);
+        if (base == MAEST_F32X3)
+            return attn_apply_launch<float, true>(qkv, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
+        return base == MAEST_F32
+                   ? attn_apply_launch<float>(qkv, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream)
+                   : attn_apply_launch<bf16_t>(qkv, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
+    }
     MAEST_REQUIRE(qkv && dout && lse && delta && dqkv, "maest_attn_bwd: null pointer");
     MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_bwd: bad shape B=%d N=%d", B, N);
     MAEST_REQUIRE(q_rows > 0 && q_rows <= N, "maest_attn_bwd_rows: q_rows = %d outside 1..N", q_rows);

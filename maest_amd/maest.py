@@ -394,6 +394,20 @@ class _Engine:
         # (per-thread overrides: the forward thread and the autograd thread of ANOTHER model in this process keep their own form)
         return ops.thread_options(gemm_wgs=wgs, gemm_tail=0) if ops.get_option("gemm_tail") == 1 else ops.thread_options(gemm_wgs=wgs)
 
+    # ---- attention rollout --------------------------------------------------------------------
+    def rollout_sweep(self, store, start: torch.Tensor, first: int, last: int, alpha: float, head_start: bool, f16: bool = False):
+        """r_{l-1} = alpha r_l + (1 - alpha) (r_l . mean_h P_l) from block `last` down to block `first` on the qkv tensors a forward retained
+        (store: _forward's `retain`): one ops.attn_apply per block -- no N x N tensor -- and one elementwise mix on [B, R, N].
+        head_start: `start` is one-hot on the head tokens, so the top block reads those two query rows only."""
+        from . import _lib as _L
+        B, N, scale, x3m, qs = store["mode"]
+        r = start
+        with (_L.flavour("f16") if f16 else contextlib.nullcontext()):
+            for i in range(last, first - 1, -1):
+                y = ops.attn_apply(store[i], r, B, N, scale, q_rows=HEAD_TOKENS if head_start and i == last else None, x3=x3m, q_prescaled=qs)
+                r = torch.add(r * alpha, y, alpha=1.0 - alpha)
+        return r
+
     # ---- forward ----------------------------------------------------------------------------
     def forward(self, *args, f16: bool = False, **kw):
         if f16:      # precision="fp16": the same sequence of C-ABI calls, served by libmaest_hip_f16.so for this thread (maest_amd/_lib.py: flavour)
@@ -404,11 +418,14 @@ class _Engine:
             return self._forward(*args, **kw)
 
     def _forward(self, x3: torch.Tensor, dt, *, toffset: int, tok_ft: torch.Tensor, perm, lam, stripes=None,
-                 stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, maps=None):
+                 stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, maps=None,
+                 retain=None):
         """x3: fp32 [B, F, T] on the device; tok_ft: int32 [P, 2] kept patch tokens.  Returns (outputs, ctx).
         x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3").
         maps (MAEST.attention_maps) = (out, blocks, q_rows, head_mean): for every block index in `blocks`, out[index] = the attention
-        probabilities of that block's qkv (ops.attn_probs); None: exactly the launches below."""
+        probabilities of that block's qkv (ops.attn_probs); None: exactly the launches below.
+        retain (MAEST.attention_rollout) = (store, blocks): store[index] = the qkv tensor of every block index in `blocks`, kept alive for
+        the sweep that follows (rollout_sweep), and store["mode"] = what that sweep needs to read them; None: nothing is kept."""
         m, W = self.m, (self.w_f16 if f16 else self.w)
         if x3m is None:
             x3m = m.precision == "bf16x3"
@@ -518,6 +535,9 @@ class _Engine:
                 qkv = gemm_nt(ln1, W.get(blk.attn.qkv.weight, dt), qkv_bias[i], out_dtype=dt)
             if maps is not None and i in maps[1]:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
                 maps[0][i] = ops.attn_probs(qkv, B, N, scale, q_rows=maps[2], x3=x3m, q_prescaled=qs, head_mean=maps[3])
+            if retain is not None and i in retain[1]:
+                retain[0][i] = qkv
+                retain[0]["mode"] = (B, N, scale, x3m, qs)
             tail = self.head_tail and stop_block < 0 and i == nblocks - 1
             # (training needs the backward kernel that honours the restriction; otherwise the attention stays complete
             # and only the per-token part of the block is restricted)
@@ -1541,6 +1561,72 @@ class MAEST(nn.Module):
         return AttentionMaps(outs[0], outs[-1], {i: maps[i] for i in sorted(maps)}, kw["tok_ft"], grid,
                              logits_dist=outs[1] if len(outs) == 3 else None)
 
+    def attention_rollout(self, x, start="head", blocks=None, alpha: float = 0.5, melspectrogram_input: bool = False, *,
+                          _patchout=None) -> "AttentionRollout":
+        """Attention rollout (Abnar & Zuidema): which input tokens feed the rows of `start` through the blocks,
+
+            r_last = start,    r_{l-1} = alpha r_l + (1 - alpha) (r_l . A_l),    A_l = mean over the heads of softmax(q k^T * scale) of block l,
+
+        from block `last` down to block `first`, next to the outputs of the same forward.  Each step is one weighted pooling of the block's
+        attention (ops.attn_apply: R row vectors times the head-mean matrix, formed from the block's qkv tensor without writing an N x N
+        map) and one elementwise mix.
+
+        x: everything ``forward`` accepts (the same rank dispatch, chunking and exceptions).  start: "head" -- R = 2, one-hot on the cls and
+        the dist token -- or a non-negative fp32 tensor [R, N] (shared by the clips) or [B, R, N], R <= 8, N the token count of the forward
+        (2 + the kept patches).  blocks: None (all) or a contiguous (first, last) pair; negative indices count from the end.  alpha in
+        [0, 1] weights the identity (residual) path; alpha = 1 returns `start`.  One forward under no_grad in the model's current mode and
+        precision, run eagerly on the caller's stream as ``attention_maps`` runs it (eval(): the evaluation kernels; train(): the patchout
+        draws apply and ``tokens`` says which patches were kept); then the sweep, top down, on the same stream.  logits and features are
+        those of ``forward``.  Memory: the qkv tensor of every swept block lives until the sweep ends -- 12 x B * N * 2304 elements of the
+        mode's type for a full rollout -- so split very large batches."""
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
+            raise ValueError(f"alpha must be a number in [0, 1], got {alpha!r}")
+        head_start = isinstance(start, str)
+        if head_start:
+            if start != "head":
+                raise ValueError(f"start must be 'head' or a tensor [R, N] / [B, R, N], got {start!r}")
+        else:
+            if not torch.is_tensor(start) or start.dtype != torch.float32 or start.dim() not in (2, 3):
+                raise ValueError("start must be 'head' or a float32 tensor [R, N] / [B, R, N], got "
+                                 + (f"a {start.dtype} tensor of shape {tuple(start.shape)}" if torch.is_tensor(start) else repr(start)))
+            if not 1 <= start.shape[-2] <= 8:
+                raise ValueError(f"start has R = {start.shape[-2]} rows: 1 .. 8 are served")
+            if not bool((start >= 0).all()):
+                raise ValueError("start must be non-negative (and hold no NaN)")
+        depth = len(self.blocks)
+        if blocks is None:
+            first, last = 0, depth - 1
+        else:
+            sel = list(blocks) if isinstance(blocks, (tuple, list)) else None
+            if sel is None or any(isinstance(i, bool) or not isinstance(i, int) for i in sel):
+                raise TypeError(f"blocks must be None or a (first, last) pair of ints, got {blocks!r}")
+            if len(sel) != 2:
+                raise ValueError(f"blocks must be a contiguous range given as a (first, last) pair, got {blocks!r}")
+            for i in sel:
+                if not -depth <= i < depth:
+                    raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
+            first, last = (i % depth for i in sel)
+            if first > last:
+                raise ValueError(f"blocks = {blocks!r}: first must not lie above last")
+        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
+        B, N = x3.shape[0], 2 + int(kw["tok_ft"].shape[0])
+        if not head_start and (start.shape[-1] != N or (start.dim() == 3 and start.shape[0] != B)):
+            raise ValueError(f"start has shape {tuple(start.shape)}: this forward has B = {B} clips of N = {N} tokens")
+        store = {}
+        with torch.no_grad():
+            outs, _ = self._engine.forward(x3, dt, retain=(store, frozenset(range(first, last + 1))), **kw)
+            if head_start:
+                r = torch.zeros((B, HEAD_TOKENS, N), dtype=torch.float32, device=x3.device)
+                r[:, 0, 0] = 1.0
+                r[:, 1, 1] = 1.0
+            else:
+                r = start.detach().to(x3.device)
+                r = (r.unsqueeze(0).expand(B, -1, -1) if r.dim() == 2 else r).contiguous()
+                if r.data_ptr() % 16:      # (a contiguous slice of a larger tensor: the kernel wants 16-byte aligned operands)
+                    r = r.clone()
+            r = self._engine.rollout_sweep(store, r, first, last, float(alpha), head_start, f16=bool(kw.get("f16")))
+        return AttentionRollout(r, outs[0], outs[-1], kw["tok_ft"], grid, logits_dist=outs[1] if len(outs) == 3 else None)
+
 
 class AttentionMaps:
     """What MAEST.attention_maps returns.  logits, features: the outputs of the same forward (logits_dist: the distillation head's, with
@@ -1561,11 +1647,30 @@ class AttentionMaps:
             if head is not None:
                 raise ValueError("these maps are the mean over the heads: there is no head to select")
             row = p[:, query, 2:]
-        Fp, Tp = self.grid
-        tok = self.tokens.to(device=row.device, dtype=torch.long)
-        out = torch.full(row.shape[:-1] + (Fp * Tp,), float("nan"), dtype=row.dtype, device=row.device)
-        out[..., tok[:, 0] * Tp + tok[:, 1]] = row
-        return out.reshape(row.shape[:-1] + (Fp, Tp))
+        return _scatter_on_grid(row, self.tokens, self.grid)
+
+
+def _scatter_on_grid(row: torch.Tensor, tokens: torch.Tensor, grid) -> torch.Tensor:
+    """[.., N - 2] values of the kept patch tokens -> [.., F', T'] on the complete patch grid, NaN where the forward dropped the patch."""
+    Fp, Tp = grid
+    tok = tokens.to(device=row.device, dtype=torch.long)
+    out = torch.full(row.shape[:-1] + (Fp * Tp,), float("nan"), dtype=row.dtype, device=row.device)
+    out[..., tok[:, 0] * Tp + tok[:, 1]] = row
+    return out.reshape(row.shape[:-1] + (Fp, Tp))
+
+
+class AttentionRollout:
+    """What MAEST.attention_rollout returns.  rollout: fp32 [B, R, N], detached; key token 0 is cls, 1 is dist, tokens[j] = (frequency patch,
+    time patch) of key token 2 + j; every row sums to the sum of its start row.  logits, features, logits_dist, tokens, grid: of the same
+    forward, as in AttentionMaps."""
+
+    def __init__(self, rollout, logits, features, tokens, grid, logits_dist=None):
+        self.rollout, self.logits, self.features, self.tokens, self.grid, self.logits_dist = rollout, logits, features, tokens, tuple(grid), logits_dist
+
+    def to_grid(self, row: int = 0) -> torch.Tensor:
+        """Row `row` of the rollout (start="head": 0 = cls, 1 = dist) over the patch tokens, laid out on the patch grid: [B, F', T'], NaN
+        where the forward dropped the patch."""
+        return _scatter_on_grid(self.rollout[:, row, 2:], self.tokens, self.grid)
 
 
 # --------------------------------------------------------------------------------------

@@ -414,6 +414,25 @@ def attn_probs(qkv: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3:
     return out
 
 
+def attn_apply(qkv: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False, q_prescaled=False) -> torch.Tensor:
+    """Weighted attention pooling, the step of attention rollout: Y[b, r, k] = sum_{q < q_rows} w[b, r, q] * mean_h softmax(scale q k^T)[b, h, q, k]
+    for R <= 8 fp32 weight rows w [B, R, N] (columns >= q_rows are not read) -> fp32 [B, R, N], heads summed in ascending order and scaled by
+    fp32(1 / 12).  No N x N tensor is written.  MAEST_ATTN_APPLY on maest_attn_bwd_rows; x3 / q_prescaled as in attn_fwd."""
+    _chk(qkv, w)
+    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    assert qkv.shape == (B * N, 3 * EMBED)
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
+    R = w.shape[1]
+    q_rows = N if q_rows is None else q_rows
+    y = torch.empty((B, R, N), dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
+    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.attn_apply_rows(R)
+    # (work: the score product, formed twice)
+    _timed_call("maest_attn_apply", _attn_flops(B, N, q_rows, 4.0), _p(qkv), None, _p(w), None, _p(lse2), _p(y), B, N, code, scale, q_rows,
+                _s(qkv), _entry="maest_attn_bwd_rows")
+    return y
+
+
 def attn_bwd_rows_supported(dtype, N: int) -> bool:
     """Whether maest_attn_bwd_rows serves q_rows < N for this shape (the fused bf16 kernel: include/maest_hip.h)."""
     return dtype == torch.bfloat16 and -(-N // 32) + 2 <= 12 and get_option("attn_bwd") in (0, 3)
