@@ -312,7 +312,8 @@ int maest_attn_bwd(const void* qkv, const void* out, const void* dout, const flo
  *   dqkv  = Y, fp32 [B, R, N], contiguous: the call writes exactly these elements.
  *   delta = workspace, fp32 [B, 12, N]: rows < q_rows of each (clip, head) are written with lse2 = m + log2(l), the row statistic in the
  *           log2 domain; nothing beyond them.
- *   out, lse must be NULL (MAEST_ERR_INVALID otherwise): like the maps, the call normalises by its own arithmetic.
+ *   out, lse must be NULL (MAEST_ERR_INVALID otherwise; `out` carries dO under MAEST_ATTN_APPLY_GRAD, below): like the maps, the call
+ *           normalises by its own arithmetic.
  * With c2 as for the forward (scale * log2 e; 1 under MAEST_BF16_QS) and t_h[q, k] = c2 * q_h . k_h on the operands as stored,
  *   Y[b, r, k] = fp32(1 / 12) * (((s_0 + s_1) + s_2) + ... + s_11),   s_h = sum_{q < q_rows} W[b, r, q] * 2^(t_h[q, k] - lse2_h[q]),
  * heads ascending, the order of the sum over q the kernel's own but fixed, one writer per element, no atomics: two calls are bit-identical.
@@ -320,6 +321,19 @@ int maest_attn_bwd(const void* qkv, const void* out, const void* dout, const flo
  * qkv, dout, delta, dqkv 16-byte aligned. */
 #define MAEST_ATTN_APPLY 0x400
 #define MAEST_ATTN_APPLY_ROWS(r) (((r) - 1) << 16)     /* R = 1 .. 8 weight rows */
+/* GRADIENT-WEIGHTED POOLING (the step of gradient-weighted attention rollout: Chefer, Gur & Wolf 2021, self-attention rule).
+ * MAEST_ATTN_APPLY_GRAD, valid only together with MAEST_ATTN_APPLY (alone, or with MAEST_ATTN_PROBS*: MAEST_ERR_INVALID), pools the
+ * rectified product of every probability with its gradient instead of the probability:
+ *   out   = dO, [B * N, 768] of the operand type (column = head * 64 + d), 16-byte aligned: the gradient of a scalar with respect to the
+ *           attention output, as maest_attn_bwd takes it in `dout`.  Only rows < q_rows of each clip are read; later rows may hold anything
+ *           (NaN included).  Without the flag `out` must stay NULL.
+ *   lse stays NULL; dout = W, delta = the lse2 workspace and dqkv = Y keep the meaning, the shapes and the base codes of the plain form.
+ * With p_h[q, k] = 2^(t_h[q, k] - lse2_h[q]) as above and g_h[q, k] = dO_h[q] . V_h[k] (the v columns as stored; under MAEST_BF16_QS only the
+ * q columns are pre-scaled),
+ *   Y[b, r, k] = fp32(1 / 12) * (((s_0 + s_1) + s_2) + ... + s_11),   s_h = sum_{q < q_rows} W[b, r, q] * max(p_h[q, k] * g_h[q, k], 0),
+ * in the order and with the single writer of the plain form: two calls are bit-identical.  p, g, W and the sums are fp32 in every mode;
+ * q k^T and dO V^T take the mode's arithmetic. */
+#define MAEST_ATTN_APPLY_GRAD 0x800
 int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B, int N, int dtype, float scale, int q_rows,
                         void* stream);
 int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

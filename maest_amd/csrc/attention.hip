@@ -521,6 +521,11 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_probs_kernel
 //             zero rows with W = 0 and lse2 = 0: they add exact zeros, whatever W holds there); p = 2^(c2 s - lse2[q]); acc[r] = fma(W[r][q],
 //             p, acc[r]) in a fixed order.  One writer per element of Y, no atomics: bit-reproducible.
 // P and W stay fp32; only Q K^T takes the mode's arithmetic (T, X3).  RP: the weight rows the kernel carries (R rounded up to 2, 4 or 8).
+//   GRAD (MAEST_ATTN_APPLY_GRAD, the step of gradient-weighted rollout): launch 2 pools max(P_h * dP_h, 0) instead of P_h, with
+//             dP_h[q, k] = dO_h[q] . V_h[k] -- the dP product of the backward, one more mma_rows of the same shape: the 64-query tiles of dO are
+//             staged beside the Q tiles (rows >= q_rows as zero, never read from memory), the V row of the lane's key rides as fragments beside
+//             its K row; g = dO V^T in the mode's arithmetic, a = max(p * g, 0), acc[r] = fma(W[r][q], a, acc[r]).  Everything else -- launch 1,
+//             the order of every sum, one writer per element -- is the plain form's.
 template <typename T, bool X3>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_stats_kernel(const T* __restrict__ qkv, float* __restrict__ lse2,
                                                                                         int B, int N, float sc_c2, int q_rows) {
@@ -594,14 +599,17 @@ __device__ __forceinline__ void apply_side_store(const ApplySide<RP>& sd, char* 
     }
 }
 
-template <typename T, bool X3, int RP>
-__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel(const T* __restrict__ qkv, const float* __restrict__ w,
-                                                                                  const float* __restrict__ lse2, float* __restrict__ y, int B,
-                                                                                  int N, float sc_c2, int q_rows, int R) {
+template <typename T, bool X3, int RP, bool GRAD>
+__global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+                                                                                  const float* __restrict__ w, const float* __restrict__ lse2,
+                                                                                  float* __restrict__ y, int B, int N, float sc_c2, int q_rows,
+                                                                                  int R) {
     using C = AttnCfg<T>;
     using Side = ApplySide<RP>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x Q[query][d], then 2 x { W[RP][64 queries], lse2[64 queries] }
+    // 2 x Q[query][d], GRAD: 2 x dO[query][d], then 2 x { W[RP][64 queries], lse2[64 queries] }
+    extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int SIDE_BYTES = Side::FLOATS * 4;
+    constexpr int DO_OFF = 2 * C::TILE, SIDE_OFF = (GRAD ? 4 : 2) * C::TILE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
     const int nkb = (N + 127) / 128;
@@ -611,37 +619,44 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
     const bool wave_active = key0 < N;                            // wave-uniform; the other waves only help staging the Q tiles
     const T* qbase = qkv + (int64_t)b * N * QKV_LD;
     const T* kbase = qbase + NHEADS * HD;
+    const T* vbase = qbase + 2 * NHEADS * HD;
+    const T* dobase = GRAD ? dout + (int64_t)b * N * OUT_LD : nullptr;   // dO[b]: [N, 768], column = head * 64 + d
     const float* w_clip = w + (int64_t)b * R * N;
     const float* lse2_clip = lse2 + (int64_t)b * NHEADS * N;
 
     const int nqt = (q_rows + 63) / 64;
     const int nsteps = NHEADS * nqt;                              // (head, query tile), double-buffered across all of them
     const float c2 = sc_c2;
-    chunk16 kf[C::STEPS];
+    chunk16 kf[C::STEPS], vf[C::STEPS];
     float acc[RP], tot[RP];
 #pragma unroll
     for (int r = 0; r < RP; ++r) { acc[r] = 0.0f; tot[r] = 0.0f; }
-    TileRegs<T> qr;
+    TileRegs<T> qr, dor;
     Side sd;
     tile_load<T>(qr, qbase, QKV_LD, 0, q_rows, tid);              // (rows >= q_rows read as zero)
+    if constexpr (GRAD) tile_load<T>(dor, dobase, OUT_LD, 0, q_rows, tid);
     apply_side_load<RP>(sd, w_clip, lse2_clip, N, R, 0, q_rows, tid);
     tile_store_rows<T>(qr, smem, tid);
-    apply_side_store<RP>(sd, smem + 2 * C::TILE, tid);
+    if constexpr (GRAD) tile_store_rows<T>(dor, smem + DO_OFF, tid);
+    apply_side_store<RP>(sd, smem + SIDE_OFF, tid);
     __syncthreads();
     int hh = 0, qt = 0;
     for (int it = 0; it < nsteps; ++it) {
         const char* q_lds = smem + (it & 1) * C::TILE;
-        const float* side = reinterpret_cast<const float*>(smem + 2 * C::TILE + (it & 1) * SIDE_BYTES);
+        const char* do_lds = smem + DO_OFF + (it & 1) * C::TILE;
+        const float* side = reinterpret_cast<const float*>(smem + SIDE_OFF + (it & 1) * SIDE_BYTES);
         int hh_n = hh, qt_n = qt + 1;
         if (qt_n == nqt) { qt_n = 0; ++hh_n; }
         const bool more = it + 1 < nsteps;
         if (more) {
             tile_load<T>(qr, qbase + hh_n * HD, QKV_LD, qt_n * 64, q_rows, tid);
+            if constexpr (GRAD) tile_load<T>(dor, dobase + hh_n * HD, OUT_LD, qt_n * 64, q_rows, tid);
             apply_side_load<RP>(sd, w_clip, lse2_clip + (int64_t)hh_n * N, N, R, qt_n * 64, q_rows, tid);
         }
         if (wave_active) {
             if (qt == 0) {
                 row_frags_load<T>(kf, kbase + hh * HD, QKV_LD, key, N, h);   // (keys >= N: a clamped row, never stored)
+                if constexpr (GRAD) row_frags_load<T>(vf, vbase + hh * HD, QKV_LD, key, N, h);
 #pragma unroll
                 for (int r = 0; r < RP; ++r) acc[r] = 0.0f;
             }
@@ -652,6 +667,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[r] = 0.0f;
                 mma_rows<T, X3>(s, q_lds, qb * 32, lane, kf);
+                f32x16_t dp;                                   // GRAD: dP[q][key] = dO[q] . V[key] of the same 32 queries
+                if constexpr (GRAD) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) dp[r] = 0.0f;
+                    mma_rows<T, X3>(dp, do_lds, qb * 32, lane, vf);
+                }
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int qo = qb * 32 + 8 * g + 4 * h;
@@ -659,7 +680,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
                     const f32x2_t c2v = {c2, c2}, n0 = {-ls.x, -ls.y}, n1 = {-ls.z, -ls.w};
                     const f32x2_t s0 = {s[4 * g], s[4 * g + 1]}, s1 = {s[4 * g + 2], s[4 * g + 3]};
                     const f32x2_t e0 = __builtin_elementwise_fma(s0, c2v, n0), e1 = __builtin_elementwise_fma(s1, c2v, n1);
-                    const float p0 = fast_exp2<T>(e0[0]), p1 = fast_exp2<T>(e0[1]), p2 = fast_exp2<T>(e1[0]), p3 = fast_exp2<T>(e1[1]);
+                    float p0 = fast_exp2<T>(e0[0]), p1 = fast_exp2<T>(e0[1]), p2 = fast_exp2<T>(e1[0]), p3 = fast_exp2<T>(e1[1]);
+                    if constexpr (GRAD) {                      // a = max(p * dP, 0): one rounding, then the rectifier
+                        p0 = fmaxf(p0 * dp[4 * g], 0.0f);
+                        p1 = fmaxf(p1 * dp[4 * g + 1], 0.0f);
+                        p2 = fmaxf(p2 * dp[4 * g + 2], 0.0f);
+                        p3 = fmaxf(p3 * dp[4 * g + 3], 0.0f);
+                    }
 #pragma unroll
                     for (int r = 0; r < RP; ++r) {
                         const float4 wv = *reinterpret_cast<const float4*>(side + r * 64 + qo);
@@ -678,7 +705,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
         }
         if (more) {
             tile_store_rows<T>(qr, smem + ((it + 1) & 1) * C::TILE, tid);
-            apply_side_store<RP>(sd, smem + 2 * C::TILE + ((it + 1) & 1) * SIDE_BYTES, tid);
+            if constexpr (GRAD) tile_store_rows<T>(dor, smem + DO_OFF + ((it + 1) & 1) * C::TILE, tid);
+            apply_side_store<RP>(sd, smem + SIDE_OFF + ((it + 1) & 1) * SIDE_BYTES, tid);
         }
         __syncthreads();
         hh = hh_n; qt = qt_n;
@@ -2067,29 +2095,36 @@ static int attn_probs_launch(const void* qkv, void* out, int B, int N, AttnScale
     return check_launch("maest_attn_fwd(probabilities)");
 }
 
-template <typename T, bool X3, int RP>
-static void attn_apply_launch_rows(const void* qkv, const float* w, const float* lse2, float* y, int B, int N, float c2, int q_rows, int R,
-                                   hipStream_t st) {
+template <typename T, bool X3, int RP, bool GRAD>
+static void attn_apply_launch_rows(const void* qkv, const void* dout, const float* w, const float* lse2, float* y, int B, int N, float c2,
+                                   int q_rows, int R, hipStream_t st) {
     using C = AttnCfg<T>;
-    const int smem_bytes = 2 * C::TILE + 2 * ApplySide<RP>::FLOATS * 4;
+    const int smem_bytes = (GRAD ? 4 : 2) * C::TILE + 2 * ApplySide<RP>::FLOATS * 4;
     static DeviceOnce once;
-    ensure_dynamic_lds(once, &attn_apply_kernel<T, X3, RP>, smem_bytes);
-    hipLaunchKernelGGL((attn_apply_kernel<T, X3, RP>), dim3(((N + 127) / 128) * B), dim3(256), smem_bytes, st, (const T*)qkv, w, lse2, y, B, N, c2,
-                       q_rows, R);
+    ensure_dynamic_lds(once, &attn_apply_kernel<T, X3, RP, GRAD>, smem_bytes);
+    hipLaunchKernelGGL((attn_apply_kernel<T, X3, RP, GRAD>), dim3(((N + 127) / 128) * B), dim3(256), smem_bytes, st, (const T*)qkv,
+                       (const T*)dout, w, lse2, y, B, N, c2, q_rows, R);
+}
+template <typename T, bool X3, bool GRAD>
+static void attn_apply_launch_form(const void* qkv, const void* dout, const float* w, const float* lse2, float* y, int B, int N, float c2,
+                                   int q_rows, int R, hipStream_t st) {
+    if (R <= 2) attn_apply_launch_rows<T, X3, 2, GRAD>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
+    else if (R <= 4) attn_apply_launch_rows<T, X3, 4, GRAD>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
+    else attn_apply_launch_rows<T, X3, 8, GRAD>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
 }
 
-// MAEST_ATTN_APPLY: w fp32 [B, R, N], lse2 fp32 [B, 12, N] (workspace: written by the first launch, read by the second), y fp32 [B, R, N]
+// MAEST_ATTN_APPLY: w fp32 [B, R, N], lse2 fp32 [B, 12, N] (workspace: written by the first launch, read by the second), y fp32 [B, R, N];
+// dout (MAEST_ATTN_APPLY_GRAD; nullptr: the plain form): dO, [B * N, 768] of the operand type
 template <typename T, bool X3 = false>
-static int attn_apply_launch(const void* qkv, const float* w, float* lse2, float* y, int B, int N, AttnScale sc, int q_rows, int R,
-                             hipStream_t st) {
+static int attn_apply_launch(const void* qkv, const void* dout, const float* w, float* lse2, float* y, int B, int N, AttnScale sc, int q_rows,
+                             int R, hipStream_t st) {
     using C = AttnCfg<T>;
     static DeviceOnce once;
     ensure_dynamic_lds(once, &attn_apply_stats_kernel<T, X3>, 2 * C::TILE);
     hipLaunchKernelGGL((attn_apply_stats_kernel<T, X3>), dim3(((q_rows + 127) / 128) * NHEADS * B), dim3(256), 2 * C::TILE, st, (const T*)qkv, lse2,
                        B, N, sc.c2, q_rows);
-    if (R <= 2) attn_apply_launch_rows<T, X3, 2>(qkv, w, lse2, y, B, N, sc.c2, q_rows, R, st);
-    else if (R <= 4) attn_apply_launch_rows<T, X3, 4>(qkv, w, lse2, y, B, N, sc.c2, q_rows, R, st);
-    else attn_apply_launch_rows<T, X3, 8>(qkv, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    if (dout != nullptr) attn_apply_launch_form<T, X3, true>(qkv, dout, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    else attn_apply_launch_form<T, X3, false>(qkv, nullptr, w, lse2, y, B, N, sc.c2, q_rows, R, st);
     return check_launch("maest_attn_bwd(apply)");
 }
 
@@ -2212,20 +2247,24 @@ extern "C" int maest_attn_bwd_rows(const void* qkv, const void* out, const void*
         MAEST_REQUIRE(qkv && dout && delta && dqkv, "maest_attn_bwd: null pointer");
         MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_bwd: bad shape B=%d N=%d", B, N);
         MAEST_REQUIRE(q_rows > 0 && q_rows <= N, "maest_attn_bwd_rows: q_rows = %d outside 1..N", q_rows);
-        MAEST_REQUIRE(out == nullptr && lse == nullptr, "maest_attn_bwd: MAEST_ATTN_APPLY reads no out and no lse: pass NULL");
+        const bool grad = (dtype & MAEST_ATTN_APPLY_GRAD) != 0;     // gradient-weighted: out = dO
+        MAEST_REQUIRE(grad || out == nullptr, "maest_attn_bwd: MAEST_ATTN_APPLY reads no out and no lse: pass NULL");
+        MAEST_REQUIRE(lse == nullptr, "maest_attn_bwd: MAEST_ATTN_APPLY reads no out and no lse: pass NULL");
+        MAEST_REQUIRE(!grad || out != nullptr, "maest_attn_bwd: null pointer (MAEST_ATTN_APPLY_GRAD reads dO from `out`)");
         MAEST_REQUIRE(base != MAEST_F32X3_A3, "maest_attn_bwd: MAEST_ATTN_APPLY keeps fp32 probabilities: no MAEST_F32X3_A3 form");
-        MAEST_REQUIRE((dtype & ~(0xFF | MAEST_ATTN_APPLY | 0xFF0000)) == 0 &&
+        MAEST_REQUIRE((dtype & ~(0xFF | MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD | 0xFF0000)) == 0 &&
                           (base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS),
-                      "maest_attn_bwd: bad dtype %d under MAEST_ATTN_APPLY", dtype & ~(MAEST_ATTN_APPLY | 0xFF0000));
+                      "maest_attn_bwd: bad dtype %d under MAEST_ATTN_APPLY", dtype & ~(MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD | 0xFF0000));
         MAEST_REQUIRE(rows <= 8, "maest_attn_bwd: MAEST_ATTN_APPLY_ROWS: %d weight rows outside 1..8", rows);
-        MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)delta % 16) == 0 && ((uintptr_t)dqkv % 16) == 0,
+        MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)delta % 16) == 0 && ((uintptr_t)dqkv % 16) == 0 &&
+                          ((uintptr_t)out % 16) == 0,
                       "maest_attn_bwd: 16-byte alignment");
         const AttnScale sca = attn_scale(scale, base == MAEST_BF16_QS);
         if (base == MAEST_F32X3)
-            return attn_apply_launch<float, true>(qkv, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
+            return attn_apply_launch<float, true>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
         return base == MAEST_F32
-                   ? attn_apply_launch<float>(qkv, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream)
-                   : attn_apply_launch<bf16_t>(qkv, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
+                   ? attn_apply_launch<float>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream)
+                   : attn_apply_launch<bf16_t>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
     }
     MAEST_REQUIRE(qkv && dout && lse && delta && dqkv, "maest_attn_bwd: null pointer");
     MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_bwd: bad shape B=%d N=%d", B, N);

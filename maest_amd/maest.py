@@ -408,6 +408,94 @@ class _Engine:
                 r = torch.add(r * alpha, y, alpha=1.0 - alpha)
         return r
 
+    # ---- gradient-weighted rollout --------------------------------------------------------------
+    def relevance_walk(self, ctx, grads_out, start: torch.Tensor, first: int, last: int, head_start: bool, grad_scale: float):
+        """r_last = start,  r_{l-1} = r_l + r_l . mean_h max(P_l * dP_l, 0)  from block `last` down to block `first`, dP_l the gradient of
+        s = sum(grads_out * outputs) / grad_scale with respect to block l's attention probabilities: the dgrad chain of _backward on the
+        activations an `explain` forward saved (ctx), with one ops.attn_relevance right after block l's `dao` exists -- no N x N tensor.
+        The walk ends behind the step of block `first`; it launches no weight-gradient GEMM, reports no gradient, touches no p.grad and
+        uses neither a side stream nor a sink (the LayerNorm kernels' gamma / beta sums land in one scratch buffer that is dropped).
+        Activations are released as the walk passes."""
+        if ctx.get("f16"):
+            from . import _lib as _L
+            with _L.flavour("f16"), self._gemm_form(shared=False, wgs=self.bwd_gemm_wgs), self._deterministic_form():
+                return self._relevance_walk(ctx, grads_out, start, first, last, head_start, grad_scale)
+        with self._gemm_form(shared=False, wgs=self.bwd_gemm_wgs), self._deterministic_form():
+            return self._relevance_walk(ctx, grads_out, start, first, last, head_start, grad_scale)
+
+    def _relevance_walk(self, ctx, grads_out, start, first, last, head_start, grad_scale):
+        m, W = self.m, (self.w_f16 if ctx.get("f16") else self.w)
+        x3m, qs = ctx["x3m"], ctx["qs"]
+        gemm_nt = partial(ops.gemm_nt, x3=x3m)
+        dt, B, N = ctx["dt"], ctx["B"], ctx["N"]
+        dev = ctx["cols"].device
+        lp = None if dt == torch.float32 else dt
+        inv = 1.0 / grad_scale
+        junk = torch.zeros((2, EMBED_DIM), dtype=torch.float32, device=dev)      # gamma / beta sums nobody reads
+        C = m.head[1].out_features
+        cpad = ops.round_up(C, 64)
+
+        def head_linear_dgrad(dlogits, lin, out_dtype):
+            dl = ops.cast_rows(dlogits, dt, cpad)
+            return gemm_nt(dl, W.get(lin.weight, dt, transposed=True, pad_cols_to=64), None, out_dtype=out_dtype, M=B, N=EMBED_DIM, K=cpad)
+
+        hn = m.head[0]
+        d_cls = d_dist = dfeat = None
+        if m.distilled_type == "mean":
+            dhl = head_linear_dgrad(grads_out[0], m.head[1], dt)
+            dfeat, _ = ops.layernorm_bwd(dhl, ctx["feat"], hn.weight, ctx["hmean"], ctx["hrstd"], None, junk[0], junk[1])
+        else:
+            if grads_out[0] is not None:
+                dhl = head_linear_dgrad(grads_out[0], m.head[1], dt)
+                d_cls, _ = ops.layernorm_bwd(dhl, ctx["cls"], hn.weight, ctx["hmean"], ctx["hrstd"], None, junk[0], junk[1])
+            if grads_out[1] is not None:
+                d_dist = head_linear_dgrad(grads_out[1], m.head_dist, torch.float32)
+        dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"],
+                               junk[0], junk[1]).reshape(-1, EMBED_DIM)
+        dx_lp = dx if dt == torch.float32 else ops.cast_weights(dx, dt)[0]
+
+        r = start
+        for i in reversed(range(first, len(m.blocks))):
+            blk, s = m.blocks[i], ctx["blocks"][i]
+            dh = gemm_nt(dx_lp, W.get(blk.mlp.fc2.weight, dt, transposed=True), None, out_dtype=dt, epi=ops.EPI_MUL, aux_in=s["h"])
+            dln2 = gemm_nt(dh, W.get(blk.mlp.fc1.weight, dt, transposed=True), None, out_dtype=dt)
+            dx1, dx1_lp = ops.layernorm_bwd(dln2, s["x1"], blk.norm2.weight, s["mean2"], s["rstd2"], dx, junk[0], junk[1], lp_dtype=lp)
+            if dt == torch.float32:
+                dx1_lp = dx1
+            wt_proj = W.get(blk.attn.proj.weight, dt, transposed=True)
+            below = i > first          # the chain goes on below this block: its attention backward runs
+            delta = None
+            if s["tail"]:
+                dao = gemm_nt(dx1_lp, wt_proj, None, out_dtype=dt)
+                dao = ops.scatter_head_rows(dao, B, N, HEAD_TOKENS, min(32, N) if s["q_rows"] else N)
+            elif below and self.fold_delta:
+                dao, delta = ops.gemm_nt_rowdot(dx1_lp, wt_proj, s["ao_full"], N, out_dtype=dt, x3=x3m)
+            else:
+                dao = gemm_nt(dx1_lp, wt_proj, None, out_dtype=dt)
+            if i <= last:
+                # behind a head-rows block only the head tokens' queries have a gradient (the other rows of dao are zero or unwritten);
+                # a one-hot start reads those two rows at the top of the sweep as well
+                q_rows = HEAD_TOKENS if s["tail"] or (head_start and i == last) else None
+                y = ops.attn_relevance(s["qkv"], dao, r, B, N, blk.attn.scale, q_rows=q_rows, x3=x3m, q_prescaled=qs)
+                r = torch.add(r, y, alpha=inv)
+            if not below:
+                break
+            if s["tail"]:
+                dqkv = ops.attn_bwd(s["qkv"], s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, q_rows=s["q_rows"], x3=x3m, q_prescaled=qs)
+            elif delta is not None:
+                dqkv = ops.attn_bwd(s["qkv"], None, dao, s["lse"], B, N, blk.attn.scale, x3=x3m, delta=delta, q_prescaled=qs)
+            else:
+                dqkv = ops.attn_bwd(s["qkv"], s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, x3=x3m, q_prescaled=qs)
+            dln1 = gemm_nt(dqkv, W.get(blk.attn.qkv.weight, dt, transposed=True), None, out_dtype=dt)
+            dx, dx_lp = ops.layernorm_bwd(dln1, s["x"], blk.norm1.weight, s["mean1"], s["rstd1"], dx1, junk[0], junk[1], lp_dtype=lp,
+                                          head_tokens=(N, HEAD_TOKENS) if s["tail"] else None)
+            if dt == torch.float32:
+                dx_lp = dx
+            s.clear()
+        for s in ctx["blocks"]:
+            s.clear()
+        return r
+
     # ---- forward ----------------------------------------------------------------------------
     def forward(self, *args, f16: bool = False, **kw):
         if f16:      # precision="fp16": the same sequence of C-ABI calls, served by libmaest_hip_f16.so for this thread (maest_amd/_lib.py: flavour)
@@ -419,13 +507,16 @@ class _Engine:
 
     def _forward(self, x3: torch.Tensor, dt, *, toffset: int, tok_ft: torch.Tensor, perm, lam, stripes=None,
                  stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, maps=None,
-                 retain=None):
+                 retain=None, explain: bool = False):
         """x3: fp32 [B, F, T] on the device; tok_ft: int32 [P, 2] kept patch tokens.  Returns (outputs, ctx).
         x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3").
         maps (MAEST.attention_maps) = (out, blocks, q_rows, head_mean): for every block index in `blocks`, out[index] = the attention
         probabilities of that block's qkv (ops.attn_probs); None: exactly the launches below.
         retain (MAEST.attention_rollout) = (store, blocks): store[index] = the qkv tensor of every block index in `blocks`, kept alive for
-        the sweep that follows (rollout_sweep), and store["mode"] = what that sweep needs to read them; None: nothing is kept."""
+        the sweep that follows (rollout_sweep), and store["mode"] = what that sweep needs to read them; None: nothing is kept.
+        explain (MAEST.attention_relevance, with save): the activations are kept for a walk that updates no weight (relevance_walk) -- the
+        operand copies are cached as an evaluation forward caches them, and no dropout / drop-path is drawn (the step counter stays)."""
+        recording = save and not explain      # a forward behind which an optimizer may step
         m, W = self.m, (self.w_f16 if f16 else self.w)
         if x3m is None:
             x3m = m.precision == "bf16x3"
@@ -440,16 +531,16 @@ class _Engine:
         # fused=True), multi-tensor kernels in general) update parameters in place WITHOUT bumping them -- a stale
         # bf16 copy then keeps training on the initial weights.  So every training-mode forward recasts everything
         # (one 0.24 ms launch for the 48 block matrices), and the first eval forward after one does too.
-        if save:
+        if recording:
             self._train_forwards += 1
-        if save or W.seen_train != self._train_forwards:
+        if recording or W.seen_train != self._train_forwards:
             W.clear()
             # a cache a TRAINING forward fills is stale for every later forward (the optimizer steps behind it): -1 matches no count, so the
             # first forward after it -- evaluation or training -- recasts; a cache an evaluation forward fills serves until the next training one.
             # (Round 6 first stored the count here in both cases: an evaluation forward behind a fused-optimizer step then ran on the weights of
             # one step earlier -- bench.py's training cases showed it as deviation_vs_fp32 1e-2 instead of 2e-3.)
-            W.seen_train = -1 if save else self._train_forwards
-        self._weights_dirty = bool(save)
+            W.seen_train = -1 if recording else self._train_forwards
+        self._weights_dirty = bool(recording)
         mats = [lin.weight for blk in m.blocks for lin in (blk.attn.qkv, blk.attn.proj, blk.mlp.fc1, blk.mlp.fc2)]
         mats += [m.patch_embed.proj.weight, m.head[1].weight]
         if m.distilled_type == "separated":
@@ -466,7 +557,7 @@ class _Engine:
             qkv_bias = [next(scaled) if b is not None else None for b in qkv_bias]
         fast3 = bool(self.x3_fast) and x3m and not save
         # dropout / stochastic depth (recording train() forwards with a rate > 0; None otherwise: exactly the launches below)
-        plan = m._regulariser_plan() if save else None
+        plan = m._regulariser_plan() if recording else None
         reg = None
         if plan is not None:
             # (seed, step) of THIS forward, written on its stream; the state's step moves on in the same launch (csrc/regularise.hip)
@@ -1292,7 +1383,8 @@ class MAEST(nn.Module):
     def _resolve_call(self, x, melspectrogram_input, _mixup, _patchout, _specmask, recording=None):
         """What a forward call resolves before it launches anything: the rank dispatch, the shape checks, the numeric mode, the kept
         tokens and the private hooks -> (x3 [B, F, T] on the device, compute dtype, the engine's keyword arguments, whether a graph is
-        recorded, (F', T') of the patch grid).  recording=False (attention_maps): never record, whatever grad mode says."""
+        recorded, (F', T') of the patch grid).  recording=False (attention_maps): never record, whatever grad mode says; "always"
+        (attention_relevance): the mode of a recording forward of the current train() / eval() state, whatever grad mode says."""
         x = self._prepare_input(x, melspectrogram_input)
         if x.dim() != 4 or x.shape[1] != 1:
             raise Exception(f"expected input of shape [B, 1, F, T], got {tuple(x.shape)}")
@@ -1317,7 +1409,9 @@ class MAEST(nn.Module):
         # embedding of block k alike (the reference's forward_features is ordinary autograd, models/maest.py:808-829)
         need_grad = (recording is not False and torch.is_grad_enabled()
                      and (x3.requires_grad or any(p.requires_grad for p in self.parameters())))
-        if need_grad and not self.training and self.precision in ("fp16", "float16", "half"):
+        if recording == "always":
+            need_grad = True      # (an explicit call: precision="fp16" runs in half in eval() too)
+        elif need_grad and not self.training and self.precision in ("fp16", "float16", "half"):
             need_grad = False     # precision="fp16": eval() forwards record no graph even outside no_grad (a backward through them fails loudly
                                   # on outputs that do not require grad); a train() forward records in half and wants a scaled loss (_resolve_precision)
         dt = self._compute_dtype(need_grad)
@@ -1581,6 +1675,66 @@ class MAEST(nn.Module):
         mode's type for a full rollout -- so split very large batches."""
         if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
             raise ValueError(f"alpha must be a number in [0, 1], got {alpha!r}")
+        head_start, first, last = self._check_sweep(start, blocks)
+        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
+        B, N = x3.shape[0], 2 + int(kw["tok_ft"].shape[0])
+        if not head_start and (start.shape[-1] != N or (start.dim() == 3 and start.shape[0] != B)):
+            raise ValueError(f"start has shape {tuple(start.shape)}: this forward has B = {B} clips of N = {N} tokens")
+        store = {}
+        with torch.no_grad():
+            outs, _ = self._engine.forward(x3, dt, retain=(store, frozenset(range(first, last + 1))), **kw)
+            r = self._sweep_start(start, head_start, B, N, x3.device)
+            r = self._engine.rollout_sweep(store, r, first, last, float(alpha), head_start, f16=bool(kw.get("f16")))
+        return AttentionRollout(r, outs[0], outs[-1], kw["tok_ft"], grid, logits_dist=outs[1] if len(outs) == 3 else None)
+
+    def attention_relevance(self, x, target, start="head", blocks=None, melspectrogram_input: bool = False, *, target_dist=None,
+                            grad_scale: float = 1.0, _patchout=None) -> "AttentionRelevance":
+        """Gradient-weighted attention rollout (Chefer, Gur & Wolf 2021, the self-attention rule): which input tokens make the model say
+        `target`.  With s = sum(target * logits), P_h the attention probabilities of a block's head and dP_h = ds / dP_h,
+
+            r_last = start,    r_{l-1} = r_l + r_l . A_l,    A_l = mean over the heads of max(P_h * dP_h, 0) of block l,
+
+        from block `last` down to block `first`, next to the outputs of the same forward.  Each step is one ops.attn_relevance on the
+        block's qkv tensor and on the gradient of s with respect to its attention output, which the walk forms as a backward would
+        (the input-gradient chain only): no N x N tensor is written, no weight gradient is computed, no .grad is touched and no graph
+        is recorded; the walk ends at block `first`.
+
+        x, start, blocks: as in ``attention_rollout``.  target: an int class index (every clip), an integer tensor [B] of class indices,
+        or a float tensor [C] / [B, C] of weights on the logits.  target_dist (distilled_type="separated" only): the same forms, on
+        logits_dist.  grad_scale: a positive power of two; the seed is multiplied by it and every pooled step divided by it -- exact in
+        fp32, there so that precision="fp16" gradients do not underflow.  The forward runs in the mode a grad-enabled ``forward`` of the
+        model's current train() / eval() state would (precision="fp16": in half in eval() too); dropout and drop-path are not applied and
+        their step counter does not move; patchout applies in train(), as for the maps.  Memory: the activations of a training forward."""
+        head_start, first, last = self._check_sweep(start, blocks)
+        C = self.head[1].out_features
+        _check_target(target, C, "target")
+        if target_dist is not None:
+            if self.distilled_type != "separated":
+                raise ValueError(f"target_dist needs distilled_type='separated': this model's is {self.distilled_type!r}")
+            _check_target(target_dist, self.head_dist.out_features, "target_dist")
+        if (isinstance(grad_scale, bool) or not isinstance(grad_scale, (int, float)) or not 0.0 < float(grad_scale) < float("inf")
+                or math.frexp(float(grad_scale))[0] != 0.5):
+            raise ValueError(f"grad_scale must be a positive power of two, got {grad_scale!r}")
+        if torch.is_tensor(x) and x.dim() in (3, 4):      # a mel batch says how many clips it holds before anything is launched
+            for t, what in ((target, "target"), (target_dist, "target_dist")):
+                _check_target_clips(t, x.shape[0], what)
+        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording="always")
+        B, N = x3.shape[0], 2 + int(kw["tok_ft"].shape[0])
+        if not head_start and (start.shape[-1] != N or (start.dim() == 3 and start.shape[0] != B)):
+            raise ValueError(f"start has shape {tuple(start.shape)}: this forward has B = {B} clips of N = {N} tokens")
+        seeds = [_target_seed(target, B, C, "target", x3.device, float(grad_scale))]
+        if self.distilled_type == "separated":
+            seeds.append(None if target_dist is None else
+                         _target_seed(target_dist, B, self.head_dist.out_features, "target_dist", x3.device, float(grad_scale)))
+        seeds.append(None)
+        with torch.no_grad():
+            outs, ctx = self._engine.forward(x3, dt, save=True, explain=True, **kw)
+            r = self._sweep_start(start, head_start, B, N, x3.device)
+            r = self._engine.relevance_walk(ctx, tuple(seeds), r, first, last, head_start, float(grad_scale))
+        return AttentionRelevance(r, outs[0], outs[-1], kw["tok_ft"], grid, logits_dist=outs[1] if len(outs) == 3 else None)
+
+    def _check_sweep(self, start, blocks):
+        """The checks ``attention_rollout`` makes on `start` and `blocks` before any device work -> (head_start, first, last)."""
         head_start = isinstance(start, str)
         if head_start:
             if start != "head":
@@ -1595,37 +1749,30 @@ class MAEST(nn.Module):
                 raise ValueError("start must be non-negative (and hold no NaN)")
         depth = len(self.blocks)
         if blocks is None:
-            first, last = 0, depth - 1
-        else:
-            sel = list(blocks) if isinstance(blocks, (tuple, list)) else None
-            if sel is None or any(isinstance(i, bool) or not isinstance(i, int) for i in sel):
-                raise TypeError(f"blocks must be None or a (first, last) pair of ints, got {blocks!r}")
-            if len(sel) != 2:
-                raise ValueError(f"blocks must be a contiguous range given as a (first, last) pair, got {blocks!r}")
-            for i in sel:
-                if not -depth <= i < depth:
-                    raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
-            first, last = (i % depth for i in sel)
-            if first > last:
-                raise ValueError(f"blocks = {blocks!r}: first must not lie above last")
-        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
-        B, N = x3.shape[0], 2 + int(kw["tok_ft"].shape[0])
-        if not head_start and (start.shape[-1] != N or (start.dim() == 3 and start.shape[0] != B)):
-            raise ValueError(f"start has shape {tuple(start.shape)}: this forward has B = {B} clips of N = {N} tokens")
-        store = {}
-        with torch.no_grad():
-            outs, _ = self._engine.forward(x3, dt, retain=(store, frozenset(range(first, last + 1))), **kw)
-            if head_start:
-                r = torch.zeros((B, HEAD_TOKENS, N), dtype=torch.float32, device=x3.device)
-                r[:, 0, 0] = 1.0
-                r[:, 1, 1] = 1.0
-            else:
-                r = start.detach().to(x3.device)
-                r = (r.unsqueeze(0).expand(B, -1, -1) if r.dim() == 2 else r).contiguous()
-                if r.data_ptr() % 16:      # (a contiguous slice of a larger tensor: the kernel wants 16-byte aligned operands)
-                    r = r.clone()
-            r = self._engine.rollout_sweep(store, r, first, last, float(alpha), head_start, f16=bool(kw.get("f16")))
-        return AttentionRollout(r, outs[0], outs[-1], kw["tok_ft"], grid, logits_dist=outs[1] if len(outs) == 3 else None)
+            return head_start, 0, depth - 1
+        sel = list(blocks) if isinstance(blocks, (tuple, list)) else None
+        if sel is None or any(isinstance(i, bool) or not isinstance(i, int) for i in sel):
+            raise TypeError(f"blocks must be None or a (first, last) pair of ints, got {blocks!r}")
+        if len(sel) != 2:
+            raise ValueError(f"blocks must be a contiguous range given as a (first, last) pair, got {blocks!r}")
+        for i in sel:
+            if not -depth <= i < depth:
+                raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
+        first, last = (i % depth for i in sel)
+        if first > last:
+            raise ValueError(f"blocks = {blocks!r}: first must not lie above last")
+        return head_start, first, last
+
+    @staticmethod
+    def _sweep_start(start, head_start, B, N, dev):
+        if head_start:
+            r = torch.zeros((B, HEAD_TOKENS, N), dtype=torch.float32, device=dev)
+            r[:, 0, 0] = 1.0
+            r[:, 1, 1] = 1.0
+            return r
+        r = start.detach().to(dev)
+        r = (r.unsqueeze(0).expand(B, -1, -1) if r.dim() == 2 else r).contiguous()
+        return r.clone() if r.data_ptr() % 16 else r      # (a contiguous slice of a larger tensor: the kernel wants 16-byte aligned operands)
 
 
 class AttentionMaps:
@@ -1671,6 +1818,64 @@ class AttentionRollout:
         """Row `row` of the rollout (start="head": 0 = cls, 1 = dist) over the patch tokens, laid out on the patch grid: [B, F', T'], NaN
         where the forward dropped the patch."""
         return _scatter_on_grid(self.rollout[:, row, 2:], self.tokens, self.grid)
+
+
+class AttentionRelevance:
+    """What MAEST.attention_relevance returns.  relevance: fp32 [B, R, N], detached, >= start elementwise; key token 0 is cls, 1 is dist,
+    tokens[j] = (frequency patch, time patch) of key token 2 + j.  logits, features, logits_dist, tokens, grid: of the same forward, as
+    in AttentionMaps."""
+
+    def __init__(self, relevance, logits, features, tokens, grid, logits_dist=None):
+        self.relevance, self.logits, self.features, self.tokens, self.grid, self.logits_dist = relevance, logits, features, tokens, tuple(grid), logits_dist
+
+    def to_grid(self, row: int = 0) -> torch.Tensor:
+        """Row `row` of the relevance (start="head": 0 = cls, 1 = dist) over the patch tokens, laid out on the patch grid: [B, F', T'],
+        NaN where the forward dropped the patch."""
+        return _scatter_on_grid(self.relevance[:, row, 2:], self.tokens, self.grid)
+
+
+_INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+
+
+def _check_target(target, C: int, what: str):
+    """What can be said about a target of attention_relevance without the batch size: its form, the range of class indices, finiteness."""
+    if isinstance(target, bool):
+        raise TypeError(f"{what} must be an int class index, an integer tensor [B] or a float tensor [C] / [B, C], got {target!r}")
+    if isinstance(target, int):
+        if not 0 <= target < C:
+            raise ValueError(f"{what} = {target} out of range for {C} classes")
+        return
+    if not torch.is_tensor(target):
+        raise TypeError(f"{what} must be an int class index, an integer tensor [B] or a float tensor [C] / [B, C], got {target!r}")
+    if target.dtype in _INT_DTYPES:
+        if target.dim() != 1:
+            raise ValueError(f"{what}: an integer tensor holds one class index per clip, [B]; got shape {tuple(target.shape)}")
+        if target.numel() and not (0 <= int(target.min()) and int(target.max()) < C):
+            raise ValueError(f"{what} holds a class index out of range for {C} classes")
+    elif target.is_floating_point():
+        if target.dim() not in (1, 2) or target.shape[-1] != C:
+            raise ValueError(f"{what}: a float tensor holds weights on the {C} logits, [C] or [B, C]; got shape {tuple(target.shape)}")
+        if not bool(torch.isfinite(target).all()):
+            raise ValueError(f"{what} must be finite")
+    else:
+        raise TypeError(f"{what} must be an int class index, an integer tensor [B] or a float tensor [C] / [B, C], got a {target.dtype} tensor")
+
+
+def _check_target_clips(target, B: int, what: str):
+    if torch.is_tensor(target) and target.dim() == (1 if target.dtype in _INT_DTYPES else 2) and target.shape[0] != B:
+        raise ValueError(f"{what} has shape {tuple(target.shape)}: this forward has B = {B} clips")
+
+
+def _target_seed(target, B: int, C: int, what: str, dev, grad_scale: float) -> torch.Tensor:
+    """grad_scale * d(sum(target * logits)) / d logits: fp32 [B, C] on the device."""
+    _check_target_clips(target, B, what)
+    if isinstance(target, int) or target.dtype in _INT_DTYPES:
+        idx = torch.full((B,), target, dtype=torch.long) if isinstance(target, int) else target.detach().cpu().long()
+        seed = torch.zeros((B, C), dtype=torch.float32)
+        seed[torch.arange(B), idx] = grad_scale
+        return seed.to(dev)
+    seed = target.detach().to(device=dev, dtype=torch.float32) * grad_scale
+    return (seed.unsqueeze(0).expand(B, -1) if seed.dim() == 1 else seed).contiguous()
 
 
 # --------------------------------------------------------------------------------------

@@ -433,6 +433,28 @@ def attn_apply(qkv: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float,
     return y
 
 
+def attn_relevance(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False,
+                   q_prescaled=False) -> torch.Tensor:
+    """Gradient-weighted attention pooling, the step of gradient-weighted rollout: Y[b, r, k] = sum_{q < q_rows} w[b, r, q] *
+    mean_h max(P_h[q, k] * dP_h[q, k], 0), P = softmax(scale q k^T) and dP_h[q, k] = dout_h[q] . v_h[k] the gradient of the scalar behind
+    `dout` ([B * N, 768] of qkv's type: d / d(attn @ v); rows >= q_rows of a clip are not read) with respect to P.  w fp32 [B, R, N], R <= 8
+    -> fp32 [B, R, N]; no N x N tensor is written.  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD on maest_attn_bwd_rows."""
+    _chk(qkv, dout, w)
+    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    assert qkv.shape == (B * N, 3 * EMBED)
+    assert dout.dtype == qkv.dtype and dout.shape == (B * N, EMBED), (dout.dtype, tuple(dout.shape))
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
+    R = w.shape[1]
+    q_rows = N if q_rows is None else q_rows
+    y = torch.empty((B, R, N), dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
+    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.ATTN_APPLY_GRAD | _lib.attn_apply_rows(R)
+    # (work: the score product, formed twice, and the dP product)
+    _timed_call("maest_attn_relevance", _attn_flops(B, N, q_rows, 6.0), _p(qkv), _p(dout), _p(w), None, _p(lse2), _p(y), B, N, code, scale,
+                q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
+    return y
+
+
 def attn_bwd_rows_supported(dtype, N: int) -> bool:
     """Whether maest_attn_bwd_rows serves q_rows < N for this shape (the fused bf16 kernel: include/maest_hip.h)."""
     return dtype == torch.bfloat16 and -(-N // 32) + 2 <= 12 and get_option("attn_bwd") in (0, 3)
