@@ -394,127 +394,27 @@ class _Engine:
         # (per-thread overrides: the forward thread and the autograd thread of ANOTHER model in this process keep their own form)
         return ops.thread_options(gemm_wgs=wgs, gemm_tail=0) if ops.get_option("gemm_tail") == 1 else ops.thread_options(gemm_wgs=wgs)
 
-    # ---- attention rollout --------------------------------------------------------------------
-    def rollout_sweep(self, store, start: torch.Tensor, first: int, last: int, alpha: float, head_start: bool, f16: bool = False):
-        """r_{l-1} = alpha r_l + (1 - alpha) (r_l . mean_h P_l) from block `last` down to block `first` on the qkv tensors a forward retained
-        (store: _forward's `retain`): one ops.attn_apply per block -- no N x N tensor -- and one elementwise mix on [B, R, N].
-        head_start: `start` is one-hot on the head tokens, so the top block reads those two query rows only."""
-        from . import _lib as _L
-        B, N, scale, x3m, qs = store["mode"]
-        r = start
-        with (_L.flavour("f16") if f16 else contextlib.nullcontext()):
-            for i in range(last, first - 1, -1):
-                y = ops.attn_apply(store[i], r, B, N, scale, q_rows=HEAD_TOKENS if head_start and i == last else None, x3=x3m, q_prescaled=qs)
-                r = torch.add(r * alpha, y, alpha=1.0 - alpha)
-        return r
-
-    # ---- gradient-weighted rollout --------------------------------------------------------------
-    def relevance_walk(self, ctx, grads_out, start: torch.Tensor, first: int, last: int, head_start: bool, grad_scale: float):
-        """r_last = start,  r_{l-1} = r_l + r_l . mean_h max(P_l * dP_l, 0)  from block `last` down to block `first`, dP_l the gradient of
-        s = sum(grads_out * outputs) / grad_scale with respect to block l's attention probabilities: the dgrad chain of _backward on the
-        activations an `explain` forward saved (ctx), with one ops.attn_relevance right after block l's `dao` exists -- no N x N tensor.
-        The walk ends behind the step of block `first`; it launches no weight-gradient GEMM, reports no gradient, touches no p.grad and
-        uses neither a side stream nor a sink (the LayerNorm kernels' gamma / beta sums land in one scratch buffer that is dropped).
-        Activations are released as the walk passes."""
-        if ctx.get("f16"):
-            from . import _lib as _L
-            with _L.flavour("f16"), self._gemm_form(shared=False, wgs=self.bwd_gemm_wgs), self._deterministic_form():
-                return self._relevance_walk(ctx, grads_out, start, first, last, head_start, grad_scale)
-        with self._gemm_form(shared=False, wgs=self.bwd_gemm_wgs), self._deterministic_form():
-            return self._relevance_walk(ctx, grads_out, start, first, last, head_start, grad_scale)
-
-    def _relevance_walk(self, ctx, grads_out, start, first, last, head_start, grad_scale):
-        m, W = self.m, (self.w_f16 if ctx.get("f16") else self.w)
-        x3m, qs = ctx["x3m"], ctx["qs"]
-        gemm_nt = partial(ops.gemm_nt, x3=x3m)
-        dt, B, N = ctx["dt"], ctx["B"], ctx["N"]
-        dev = ctx["cols"].device
-        lp = None if dt == torch.float32 else dt
-        inv = 1.0 / grad_scale
-        junk = torch.zeros((2, EMBED_DIM), dtype=torch.float32, device=dev)      # gamma / beta sums nobody reads
-        C = m.head[1].out_features
-        cpad = ops.round_up(C, 64)
-
-        def head_linear_dgrad(dlogits, lin, out_dtype):
-            dl = ops.cast_rows(dlogits, dt, cpad)
-            return gemm_nt(dl, W.get(lin.weight, dt, transposed=True, pad_cols_to=64), None, out_dtype=out_dtype, M=B, N=EMBED_DIM, K=cpad)
-
-        hn = m.head[0]
-        d_cls = d_dist = dfeat = None
-        if m.distilled_type == "mean":
-            dhl = head_linear_dgrad(grads_out[0], m.head[1], dt)
-            dfeat, _ = ops.layernorm_bwd(dhl, ctx["feat"], hn.weight, ctx["hmean"], ctx["hrstd"], None, junk[0], junk[1])
-        else:
-            if grads_out[0] is not None:
-                dhl = head_linear_dgrad(grads_out[0], m.head[1], dt)
-                d_cls, _ = ops.layernorm_bwd(dhl, ctx["cls"], hn.weight, ctx["hmean"], ctx["hrstd"], None, junk[0], junk[1])
-            if grads_out[1] is not None:
-                d_dist = head_linear_dgrad(grads_out[1], m.head_dist, torch.float32)
-        dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"],
-                               junk[0], junk[1]).reshape(-1, EMBED_DIM)
-        dx_lp = dx if dt == torch.float32 else ops.cast_weights(dx, dt)[0]
-
-        r = start
-        for i in reversed(range(first, len(m.blocks))):
-            blk, s = m.blocks[i], ctx["blocks"][i]
-            dh = gemm_nt(dx_lp, W.get(blk.mlp.fc2.weight, dt, transposed=True), None, out_dtype=dt, epi=ops.EPI_MUL, aux_in=s["h"])
-            dln2 = gemm_nt(dh, W.get(blk.mlp.fc1.weight, dt, transposed=True), None, out_dtype=dt)
-            dx1, dx1_lp = ops.layernorm_bwd(dln2, s["x1"], blk.norm2.weight, s["mean2"], s["rstd2"], dx, junk[0], junk[1], lp_dtype=lp)
-            if dt == torch.float32:
-                dx1_lp = dx1
-            wt_proj = W.get(blk.attn.proj.weight, dt, transposed=True)
-            below = i > first          # the chain goes on below this block: its attention backward runs
-            delta = None
-            if s["tail"]:
-                dao = gemm_nt(dx1_lp, wt_proj, None, out_dtype=dt)
-                dao = ops.scatter_head_rows(dao, B, N, HEAD_TOKENS, min(32, N) if s["q_rows"] else N)
-            elif below and self.fold_delta:
-                dao, delta = ops.gemm_nt_rowdot(dx1_lp, wt_proj, s["ao_full"], N, out_dtype=dt, x3=x3m)
-            else:
-                dao = gemm_nt(dx1_lp, wt_proj, None, out_dtype=dt)
-            if i <= last:
-                # behind a head-rows block only the head tokens' queries have a gradient (the other rows of dao are zero or unwritten);
-                # a one-hot start reads those two rows at the top of the sweep as well
-                q_rows = HEAD_TOKENS if s["tail"] or (head_start and i == last) else None
-                y = ops.attn_relevance(s["qkv"], dao, r, B, N, blk.attn.scale, q_rows=q_rows, x3=x3m, q_prescaled=qs)
-                r = torch.add(r, y, alpha=inv)
-            if not below:
-                break
-            if s["tail"]:
-                dqkv = ops.attn_bwd(s["qkv"], s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, q_rows=s["q_rows"], x3=x3m, q_prescaled=qs)
-            elif delta is not None:
-                dqkv = ops.attn_bwd(s["qkv"], None, dao, s["lse"], B, N, blk.attn.scale, x3=x3m, delta=delta, q_prescaled=qs)
-            else:
-                dqkv = ops.attn_bwd(s["qkv"], s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, x3=x3m, q_prescaled=qs)
-            dln1 = gemm_nt(dqkv, W.get(blk.attn.qkv.weight, dt, transposed=True), None, out_dtype=dt)
-            dx, dx_lp = ops.layernorm_bwd(dln1, s["x"], blk.norm1.weight, s["mean1"], s["rstd1"], dx1, junk[0], junk[1], lp_dtype=lp,
-                                          head_tokens=(N, HEAD_TOKENS) if s["tail"] else None)
-            if dt == torch.float32:
-                dx_lp = dx
-            s.clear()
-        for s in ctx["blocks"]:
-            s.clear()
-        return r
+    @contextlib.contextmanager
+    def _pass(self, f16, shared: bool = False, wgs: int = 256, deterministic: bool = False):
+        """The settings of one pass as one context.  f16 (precision="fp16"): the same sequence of C-ABI calls, served by libmaest_hip_f16.so
+        for this thread (maest_amd/_lib.py: flavour); then _gemm_form(shared, wgs); then, for a backward, _deterministic_form."""
+        none = contextlib.nullcontext()
+        with (ops._lib.flavour("f16") if f16 else none), self._gemm_form(shared, wgs), (self._deterministic_form() if deterministic else none):
+            yield
 
     # ---- forward ----------------------------------------------------------------------------
     def forward(self, *args, f16: bool = False, **kw):
-        if f16:      # precision="fp16": the same sequence of C-ABI calls, served by libmaest_hip_f16.so for this thread (maest_amd/_lib.py: flavour)
-            from . import _lib as _L
-            with _L.flavour("f16"), self._gemm_form(shared=False):
-                return self._forward(*args, f16=True, **kw)
-        with self._gemm_form(shared=False):
-            return self._forward(*args, **kw)
+        with self._pass(f16):
+            return self._forward(*args, f16=f16, **kw)
 
     def _forward(self, x3: torch.Tensor, dt, *, toffset: int, tok_ft: torch.Tensor, perm, lam, stripes=None,
-                 stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, maps=None,
-                 retain=None, explain: bool = False):
+                 stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, tap=None,
+                 explain: bool = False):
         """x3: fp32 [B, F, T] on the device; tok_ft: int32 [P, 2] kept patch tokens.  Returns (outputs, ctx).
         x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3").
-        maps (MAEST.attention_maps) = (out, blocks, q_rows, head_mean): for every block index in `blocks`, out[index] = the attention
-        probabilities of that block's qkv (ops.attn_probs); None: exactly the launches below.
-        retain (MAEST.attention_rollout) = (store, blocks): store[index] = the qkv tensor of every block index in `blocks`, kept alive for
-        the sweep that follows (rollout_sweep), and store["mode"] = what that sweep needs to read them; None: nothing is kept.
-        explain (MAEST.attention_relevance, with save): the activations are kept for a walk that updates no weight (relevance_walk) -- the
+        tap (maest_amd/explain.py: the attention maps and the rollout): called as tap(i, qkv, (B, N, scale, x3m, qs)) right behind block
+        i's qkv GEMM, with what an attention kernel needs to read that tensor; None: exactly the launches below.
+        explain (MAEST.attention_relevance, with save): the activations are kept for a backward that updates no weight -- the
         operand copies are cached as an evaluation forward caches them, and no dropout / drop-path is drawn (the step counter stays)."""
         recording = save and not explain      # a forward behind which an optimizer may step
         m, W = self.m, (self.w_f16 if f16 else self.w)
@@ -624,11 +524,8 @@ class _Engine:
                 qkv = ops.gemm_nt(ln1, w3[(i, "qkv")], qkv_bias[i], out_dtype=torch.float32, split3=True)
             else:
                 qkv = gemm_nt(ln1, W.get(blk.attn.qkv.weight, dt), qkv_bias[i], out_dtype=dt)
-            if maps is not None and i in maps[1]:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
-                maps[0][i] = ops.attn_probs(qkv, B, N, scale, q_rows=maps[2], x3=x3m, q_prescaled=qs, head_mean=maps[3])
-            if retain is not None and i in retain[1]:
-                retain[0][i] = qkv
-                retain[0]["mode"] = (B, N, scale, x3m, qs)
+            if tap is not None:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
+                tap(i, qkv, (B, N, scale, x3m, qs))
             tail = self.head_tail and stop_block < 0 and i == nblocks - 1
             # (training needs the backward kernel that honours the restriction; otherwise the attention stays complete
             # and only the per-token part of the block is restricted)
@@ -737,18 +634,15 @@ class _Engine:
         mode = self.m.deterministic_mode()
         return contextlib.nullcontext() if mode is None else ops.thread_options(deterministic=mode)
 
-    def backward(self, ctx, grads_out, sink=None):
-        if ctx.get("f16"):     # recorded by libmaest_hip_f16.so: its 16-bit tensors are IEEE half, the backward is that build's too (this thread's calls)
-            from . import _lib as _L
-            with _L.flavour("f16"), self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs), self._deterministic_form():
-                G = self._backward(ctx, grads_out, sink)
-        else:
-            with self._gemm_form(shared=sink is not None, wgs=self.bwd_gemm_wgs), self._deterministic_form():
-                G = self._backward(ctx, grads_out, sink)
-        self._step_done(ctx["cols"].device)
+    def backward(self, ctx, grads_out, sink=None, *, weights: bool = True, first=None, tap=None):
+        # (a forward recorded by libmaest_hip_f16.so holds IEEE half in its 16-bit tensors: its backward is that build's too)
+        with self._pass(ctx.get("f16"), shared=sink is not None, wgs=self.bwd_gemm_wgs, deterministic=True):
+            G = self._backward(ctx, grads_out, sink, weights, first, tap)
+        if weights:
+            self._step_done(ctx["cols"].device)
         return G
 
-    def _backward(self, ctx, grads_out, sink=None):
+    def _backward(self, ctx, grads_out, sink=None, weights: bool = True, first=None, tap=None):
         """grads_out: gradients w.r.t. the forward outputs (same tuple structure, entries may be None).
         Returns {parameter name: fp32 gradient}, plus "_input": the gradient w.r.t. the forward's input x3 when
         ctx["want_dx"] asks for it.  With a `sink` (maest_amd.dist.GradReducer) every
@@ -757,7 +651,12 @@ class _Engine:
         A forward truncated at block k (ctx["stop_block"] = k: model(x, transformer_block=k)) starts from the backward of its
         embedding pool and runs the blocks k .. 0 and the embeddings only; parameters it does not reach get no gradient (with a
         sink: they are reported complete with their zeroed buffers, like DDP's find_unused_parameters=True).  Parameters that do
-        not require grad get none either, and their weight-gradient GEMMs are not run."""
+        not require grad get none either, and their weight-gradient GEMMs are not run.
+        weights=False: the input-gradient chain alone, as if every parameter were frozen -- and no flat gradient buffer, no side stream;
+        the LayerNorm kernels' gamma / beta sums land in one scratch buffer that is dropped.
+        first: the chain returns right behind block `first`'s `dao`, before that block's attention backward; the activations of the
+        blocks below are released unread and nothing of the embeddings runs.
+        tap (maest_amd/explain.py: the relevance step): called as tap(i, saved activations of block i, dao) as soon as `dao` exists."""
         m, W = self.m, (self.w_f16 if ctx.get("f16") else self.w)
         x3m = ctx["x3m"]
         qs = ctx["qs"]
@@ -767,17 +666,19 @@ class _Engine:
         M = B * N
         dev = ctx["cols"].device
         G = {}
-        req = {n: p.requires_grad for n, p in m.named_parameters()}
+        req = {n: weights and p.requires_grad for n, p in m.named_parameters()}
         stop = ctx.get("stop_block", -1)
-        first = len(m.blocks) - 1 if stop < 0 else stop     # the last block this backward runs
+        top = len(m.blocks) - 1 if stop < 0 else stop     # the last block the forward ran: where the chain starts
         attn_only = stop >= 0 and ctx.get("self_attention", False)      # ... of which only the attention branch
 
         # without a sink, all parameter gradients of this pass are views of ONE zero-filled flat buffer (one fill
         # kernel instead of ~160; the wgrad kernels accumulate into it with split-K atomics)
         flat, layout = None, None
-        if sink is None:
+        if sink is None and weights:
             layout, total = self._grad_layout()
             flat = torch.zeros(total, dtype=torch.float32, device=dev)
+        assert first is None or not weights, "an early stop is served for the input-gradient chain alone (nothing waits for a side stream)"
+        junk = None if weights else torch.zeros((2, EMBED_DIM), dtype=torch.float32, device=dev)      # gamma / beta sums nobody reads
 
         def buf(name, *shape):
             v = sink.grad_buffer(name) if sink is not None else None
@@ -788,10 +689,13 @@ class _Engine:
                 return flat[off:off + n].view(*shape)
             return torch.zeros(*shape, dtype=torch.float32, device=dev)
 
+        def norm_bufs(prefix):      # where a LayerNorm backward adds its gamma / beta gradients
+            return (junk[0], junk[1]) if junk is not None else (buf(prefix + ".weight", EMBED_DIM), buf(prefix + ".bias", EMBED_DIM))
+
         # Weight / bias gradients are off the critical path (nothing in backward consumes them), so they run on
         # a SIDE HIP stream and overlap with the dgrad -> LayerNorm -> attention chain on the main stream: the
         # NT dgrad GEMMs are bound by their C-tile writes, the TN wgrad GEMMs by the MFMA pipe.
-        side = self._side_stream(dev) if (self.overlap_wgrad and dev.type == "cuda") else None
+        side = self._side_stream(dev) if (weights and self.overlap_wgrad and dev.type == "cuda") else None
         main = torch.cuda.current_stream(dev) if side is not None else None
 
         def done(name, g):
@@ -867,7 +771,7 @@ class _Engine:
                 return gemm_nt(dl, wt, None, out_dtype=out_dtype, M=B, N=EMBED_DIM, K=cpad)
 
             d_cls = d_dist = None
-            g_h0w, g_h0b = buf("head.0.weight", EMBED_DIM), buf("head.0.bias", EMBED_DIM)
+            g_h0w, g_h0b = norm_bufs("head.0")
             if m.distilled_type == "mean":
                 dlogits, dfeat_out = grads_out
                 dfeat = None
@@ -890,7 +794,7 @@ class _Engine:
                     d_dist = head_linear_bwd(dlogits_d.contiguous(), ctx["dist_lp"], m.head_dist, "head_dist", torch.float32)
             done("head.0.weight", g_h0w)
             done("head.0.bias", g_h0b)
-            g_nw, g_nb = buf("norm.weight", EMBED_DIM), buf("norm.bias", EMBED_DIM)
+            g_nw, g_nb = norm_bufs("norm")
             dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"],
                                    g_nw, g_nb).reshape(-1, EMBED_DIM)
             done("norm.weight", g_nw)
@@ -908,12 +812,12 @@ class _Engine:
                 return d_lp
             return ops.drop_cast(d32, dt, B, N, rpc, elem, path, reg["snap"])
 
-        for i in reversed(range(first + 1)):
+        for i in reversed(range(top + 1)):
             blk, s = m.blocks[i], ctx["blocks"][i]
             p = f"blocks.{i}."
             H = blk.mlp.fc1.out_features
             br, rpc = s.get("reg"), s.get("rpc", N)
-            if attn_only and i == first:
+            if attn_only and i == top:
                 # Block.forward(..., return_self_attention=True) = proj(attn(norm1 x)): no residual, no norm2 / MLP
                 dx1, dx1_lp, dres1 = dx, dx_lp, None
                 if br is not None:
@@ -928,7 +832,7 @@ class _Engine:
                 # fc1
                 wgrad(p + "mlp.fc1.weight", p + "mlp.fc1.bias", dh, s["ln2"], H, EMBED_DIM)
                 dln2 = gemm_nt(dh, W.get(blk.mlp.fc1.weight, dt, transposed=True), None, out_dtype=dt)
-                gw, gb = buf(p + "norm2.weight", EMBED_DIM), buf(p + "norm2.bias", EMBED_DIM)
+                gw, gb = norm_bufs(p + "norm2")
                 dx1, dx1_lp = ops.layernorm_bwd(dln2, s["x1"], blk.norm2.weight, s["mean2"], s["rstd2"], dx, gw, gb,
                                                 lp_dtype=None if dt == torch.float32 else dt)
                 done(p + "norm2.weight", gw)
@@ -941,22 +845,28 @@ class _Engine:
             # proj (+ residual)
             wgrad(p + "attn.proj.weight", p + "attn.proj.bias", dx1_lp, s["ao"], EMBED_DIM, EMBED_DIM)
             wt_proj = W.get(blk.attn.proj.weight, dt, transposed=True)
+            below = first is None or i > first      # the chain goes on below this block's dao: its attention backward runs
+            delta = None
             if s["tail"]:
                 dao = gemm_nt(dx1_lp, wt_proj, None, out_dtype=dt)
                 # back to the token-major layout: the head tokens' rows, zeros for the queries the kernel still visits
                 # (its first 32-row tile when it honours q_rows, every row otherwise)
                 dao = ops.scatter_head_rows(dao, B, N, HEAD_TOKENS, min(32, N) if s["q_rows"] else N)
-                dqkv = ops.attn_bwd(s["qkv"], s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, q_rows=s["q_rows"], x3=x3m, q_prescaled=qs)
-            elif self.fold_delta:
+            elif below and self.fold_delta:
                 # delta = rowsum(dO * O) per (clip, head, query) out of the C-tile pass of the GEMM that produces dO
                 dao, delta = ops.gemm_nt_rowdot(dx1_lp, wt_proj, s["ao_full"], N, out_dtype=dt, x3=x3m)
-                dqkv = ops.attn_bwd(s["qkv"], None, dao, s["lse"], B, N, blk.attn.scale, x3=x3m, delta=delta, q_prescaled=qs)
             else:
                 dao = gemm_nt(dx1_lp, wt_proj, None, out_dtype=dt)
-                dqkv = ops.attn_bwd(s["qkv"], s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, x3=x3m, q_prescaled=qs)
+            if tap is not None:
+                tap(i, s, dao)
+            if not below:
+                break
+            # (delta given: the kernel does not read O; q_rows is set behind a head-rows block only)
+            dqkv = ops.attn_bwd(s["qkv"], None if delta is not None else s["ao_full"], dao, s["lse"], B, N, blk.attn.scale, q_rows=s["q_rows"],
+                                x3=x3m, delta=delta, q_prescaled=qs)
             wgrad(p + "attn.qkv.weight", p + "attn.qkv.bias", dqkv, s["ln1"], 3 * EMBED_DIM, EMBED_DIM)
             dln1 = gemm_nt(dqkv, W.get(blk.attn.qkv.weight, dt, transposed=True), None, out_dtype=dt)
-            gw, gb = buf(p + "norm1.weight", EMBED_DIM), buf(p + "norm1.bias", EMBED_DIM)
+            gw, gb = norm_bufs(p + "norm1")
             dx, dx_lp = ops.layernorm_bwd(dln1, s["x"], blk.norm1.weight, s["mean1"], s["rstd1"], dres1, gw, gb,
                                           lp_dtype=None if dt == torch.float32 else dt,
                                           head_tokens=(N, HEAD_TOKENS) if s["tail"] else None)
@@ -966,6 +876,10 @@ class _Engine:
                 dx_lp = dx
             s.clear()  # release this block's activations
 
+        if first is not None:
+            for s in ctx["blocks"]:
+                s.clear()
+            return G
         if reg is not None and reg["p"] > 0:      # pos_drop, on the gradient of the assembled tokens
             ops.dropout_(dx, None, B, N, N, reg["pos_site"], reg["p"], reg["snap"])
         Tt = m.time_new_pos_embed.shape[-1]
@@ -1631,29 +1545,7 @@ class MAEST(nn.Module):
         (no two-stream split, no HIP-graph replay; the weights' operand copies are the ones every forward shares); in every requested
         block one more launch writes the map from the qkv tensor the block computed anyway (ops.attn_probs).  The maps are detached
         fp32 tensors.  `return_self_attention=True` of ``forward`` is a different tensor: proj(attn @ v) of one block, pooled."""
-        if queries not in ("head", "all"):
-            raise ValueError(f"queries must be 'head' or 'all', got {queries!r}")
-        if heads not in ("all", "mean"):
-            raise ValueError(f"heads must be 'all' or 'mean', got {heads!r}")
-        depth = len(self.blocks)
-        if blocks is None:
-            want = list(range(depth))
-        else:
-            if isinstance(blocks, (bool, str)) or not (isinstance(blocks, int) or hasattr(blocks, "__iter__")):
-                raise TypeError(f"blocks must be an int, an iterable of ints or None, got {blocks!r}")
-            want = [blocks] if isinstance(blocks, int) else list(blocks)
-            for i in want:
-                if isinstance(i, bool) or not isinstance(i, int):
-                    raise TypeError(f"blocks must be an int, an iterable of ints or None, got an element {i!r}")
-                if not -depth <= i < depth:
-                    raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
-            want = [i % depth for i in want]
-        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
-        maps = {}
-        with torch.no_grad():
-            outs, _ = self._engine.forward(x3, dt, maps=(maps, frozenset(want), HEAD_TOKENS if queries == "head" else None, heads == "mean"), **kw)
-        return AttentionMaps(outs[0], outs[-1], {i: maps[i] for i in sorted(maps)}, kw["tok_ft"], grid,
-                             logits_dist=outs[1] if len(outs) == 3 else None)
+        return explain.attention_maps(self, x, blocks, queries, heads, melspectrogram_input, _patchout=_patchout)
 
     def attention_rollout(self, x, start="head", blocks=None, alpha: float = 0.5, melspectrogram_input: bool = False, *,
                           _patchout=None) -> "AttentionRollout":
@@ -1673,19 +1565,7 @@ class MAEST(nn.Module):
         draws apply and ``tokens`` says which patches were kept); then the sweep, top down, on the same stream.  logits and features are
         those of ``forward``.  Memory: the qkv tensor of every swept block lives until the sweep ends -- 12 x B * N * 2304 elements of the
         mode's type for a full rollout -- so split very large batches."""
-        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
-            raise ValueError(f"alpha must be a number in [0, 1], got {alpha!r}")
-        head_start, first, last = self._check_sweep(start, blocks)
-        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
-        B, N = x3.shape[0], 2 + int(kw["tok_ft"].shape[0])
-        if not head_start and (start.shape[-1] != N or (start.dim() == 3 and start.shape[0] != B)):
-            raise ValueError(f"start has shape {tuple(start.shape)}: this forward has B = {B} clips of N = {N} tokens")
-        store = {}
-        with torch.no_grad():
-            outs, _ = self._engine.forward(x3, dt, retain=(store, frozenset(range(first, last + 1))), **kw)
-            r = self._sweep_start(start, head_start, B, N, x3.device)
-            r = self._engine.rollout_sweep(store, r, first, last, float(alpha), head_start, f16=bool(kw.get("f16")))
-        return AttentionRollout(r, outs[0], outs[-1], kw["tok_ft"], grid, logits_dist=outs[1] if len(outs) == 3 else None)
+        return explain.attention_rollout(self, x, start, blocks, alpha, melspectrogram_input, _patchout=_patchout)
 
     def attention_relevance(self, x, target, start="head", blocks=None, melspectrogram_input: bool = False, *, target_dist=None,
                             grad_scale: float = 1.0, _patchout=None) -> "AttentionRelevance":
@@ -1705,177 +1585,8 @@ class MAEST(nn.Module):
         fp32, there so that precision="fp16" gradients do not underflow.  The forward runs in the mode a grad-enabled ``forward`` of the
         model's current train() / eval() state would (precision="fp16": in half in eval() too); dropout and drop-path are not applied and
         their step counter does not move; patchout applies in train(), as for the maps.  Memory: the activations of a training forward."""
-        head_start, first, last = self._check_sweep(start, blocks)
-        C = self.head[1].out_features
-        _check_target(target, C, "target")
-        if target_dist is not None:
-            if self.distilled_type != "separated":
-                raise ValueError(f"target_dist needs distilled_type='separated': this model's is {self.distilled_type!r}")
-            _check_target(target_dist, self.head_dist.out_features, "target_dist")
-        if (isinstance(grad_scale, bool) or not isinstance(grad_scale, (int, float)) or not 0.0 < float(grad_scale) < float("inf")
-                or math.frexp(float(grad_scale))[0] != 0.5):
-            raise ValueError(f"grad_scale must be a positive power of two, got {grad_scale!r}")
-        if torch.is_tensor(x) and x.dim() in (3, 4):      # a mel batch says how many clips it holds before anything is launched
-            for t, what in ((target, "target"), (target_dist, "target_dist")):
-                _check_target_clips(t, x.shape[0], what)
-        x3, dt, kw, _, grid = self._resolve_call(x, melspectrogram_input, None, _patchout, None, recording="always")
-        B, N = x3.shape[0], 2 + int(kw["tok_ft"].shape[0])
-        if not head_start and (start.shape[-1] != N or (start.dim() == 3 and start.shape[0] != B)):
-            raise ValueError(f"start has shape {tuple(start.shape)}: this forward has B = {B} clips of N = {N} tokens")
-        seeds = [_target_seed(target, B, C, "target", x3.device, float(grad_scale))]
-        if self.distilled_type == "separated":
-            seeds.append(None if target_dist is None else
-                         _target_seed(target_dist, B, self.head_dist.out_features, "target_dist", x3.device, float(grad_scale)))
-        seeds.append(None)
-        with torch.no_grad():
-            outs, ctx = self._engine.forward(x3, dt, save=True, explain=True, **kw)
-            r = self._sweep_start(start, head_start, B, N, x3.device)
-            r = self._engine.relevance_walk(ctx, tuple(seeds), r, first, last, head_start, float(grad_scale))
-        return AttentionRelevance(r, outs[0], outs[-1], kw["tok_ft"], grid, logits_dist=outs[1] if len(outs) == 3 else None)
-
-    def _check_sweep(self, start, blocks):
-        """The checks ``attention_rollout`` makes on `start` and `blocks` before any device work -> (head_start, first, last)."""
-        head_start = isinstance(start, str)
-        if head_start:
-            if start != "head":
-                raise ValueError(f"start must be 'head' or a tensor [R, N] / [B, R, N], got {start!r}")
-        else:
-            if not torch.is_tensor(start) or start.dtype != torch.float32 or start.dim() not in (2, 3):
-                raise ValueError("start must be 'head' or a float32 tensor [R, N] / [B, R, N], got "
-                                 + (f"a {start.dtype} tensor of shape {tuple(start.shape)}" if torch.is_tensor(start) else repr(start)))
-            if not 1 <= start.shape[-2] <= 8:
-                raise ValueError(f"start has R = {start.shape[-2]} rows: 1 .. 8 are served")
-            if not bool((start >= 0).all()):
-                raise ValueError("start must be non-negative (and hold no NaN)")
-        depth = len(self.blocks)
-        if blocks is None:
-            return head_start, 0, depth - 1
-        sel = list(blocks) if isinstance(blocks, (tuple, list)) else None
-        if sel is None or any(isinstance(i, bool) or not isinstance(i, int) for i in sel):
-            raise TypeError(f"blocks must be None or a (first, last) pair of ints, got {blocks!r}")
-        if len(sel) != 2:
-            raise ValueError(f"blocks must be a contiguous range given as a (first, last) pair, got {blocks!r}")
-        for i in sel:
-            if not -depth <= i < depth:
-                raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
-        first, last = (i % depth for i in sel)
-        if first > last:
-            raise ValueError(f"blocks = {blocks!r}: first must not lie above last")
-        return head_start, first, last
-
-    @staticmethod
-    def _sweep_start(start, head_start, B, N, dev):
-        if head_start:
-            r = torch.zeros((B, HEAD_TOKENS, N), dtype=torch.float32, device=dev)
-            r[:, 0, 0] = 1.0
-            r[:, 1, 1] = 1.0
-            return r
-        r = start.detach().to(dev)
-        r = (r.unsqueeze(0).expand(B, -1, -1) if r.dim() == 2 else r).contiguous()
-        return r.clone() if r.data_ptr() % 16 else r      # (a contiguous slice of a larger tensor: the kernel wants 16-byte aligned operands)
-
-
-class AttentionMaps:
-    """What MAEST.attention_maps returns.  logits, features: the outputs of the same forward (logits_dist: the distillation head's, with
-    distilled_type="separated"; else None).  maps: {block index: fp32 [B, 12, Q, N] or, heads="mean", [B, Q, N]}; key token 0 is cls, 1 is
-    dist, tokens[j] = (frequency patch, time patch) of key token 2 + j (int32 [N - 2, 2]: the patches the forward kept, in sequence
-    order); grid = (F', T') of the complete patch grid."""
-
-    def __init__(self, logits, features, maps, tokens, grid, logits_dist=None):
-        self.logits, self.features, self.maps, self.tokens, self.grid, self.logits_dist = logits, features, maps, tokens, tuple(grid), logits_dist
-
-    def to_grid(self, block: int, query: int = 0, head: Optional[int] = None) -> torch.Tensor:
-        """Row `query` of block `block`'s map (0: cls, 1: dist) laid out on the patch grid: [B, F', T'] for one head (or a map of
-        heads="mean"), [B, 12, F', T'] for every head (head=None); NaN where the forward dropped the patch."""
-        p = self.maps[block]
-        if p.dim() == 4:
-            row = p[:, :, query, 2:] if head is None else p[:, head, query, 2:]
-        else:
-            if head is not None:
-                raise ValueError("these maps are the mean over the heads: there is no head to select")
-            row = p[:, query, 2:]
-        return _scatter_on_grid(row, self.tokens, self.grid)
-
-
-def _scatter_on_grid(row: torch.Tensor, tokens: torch.Tensor, grid) -> torch.Tensor:
-    """[.., N - 2] values of the kept patch tokens -> [.., F', T'] on the complete patch grid, NaN where the forward dropped the patch."""
-    Fp, Tp = grid
-    tok = tokens.to(device=row.device, dtype=torch.long)
-    out = torch.full(row.shape[:-1] + (Fp * Tp,), float("nan"), dtype=row.dtype, device=row.device)
-    out[..., tok[:, 0] * Tp + tok[:, 1]] = row
-    return out.reshape(row.shape[:-1] + (Fp, Tp))
-
-
-class AttentionRollout:
-    """What MAEST.attention_rollout returns.  rollout: fp32 [B, R, N], detached; key token 0 is cls, 1 is dist, tokens[j] = (frequency patch,
-    time patch) of key token 2 + j; every row sums to the sum of its start row.  logits, features, logits_dist, tokens, grid: of the same
-    forward, as in AttentionMaps."""
-
-    def __init__(self, rollout, logits, features, tokens, grid, logits_dist=None):
-        self.rollout, self.logits, self.features, self.tokens, self.grid, self.logits_dist = rollout, logits, features, tokens, tuple(grid), logits_dist
-
-    def to_grid(self, row: int = 0) -> torch.Tensor:
-        """Row `row` of the rollout (start="head": 0 = cls, 1 = dist) over the patch tokens, laid out on the patch grid: [B, F', T'], NaN
-        where the forward dropped the patch."""
-        return _scatter_on_grid(self.rollout[:, row, 2:], self.tokens, self.grid)
-
-
-class AttentionRelevance:
-    """What MAEST.attention_relevance returns.  relevance: fp32 [B, R, N], detached, >= start elementwise; key token 0 is cls, 1 is dist,
-    tokens[j] = (frequency patch, time patch) of key token 2 + j.  logits, features, logits_dist, tokens, grid: of the same forward, as
-    in AttentionMaps."""
-
-    def __init__(self, relevance, logits, features, tokens, grid, logits_dist=None):
-        self.relevance, self.logits, self.features, self.tokens, self.grid, self.logits_dist = relevance, logits, features, tokens, tuple(grid), logits_dist
-
-    def to_grid(self, row: int = 0) -> torch.Tensor:
-        """Row `row` of the relevance (start="head": 0 = cls, 1 = dist) over the patch tokens, laid out on the patch grid: [B, F', T'],
-        NaN where the forward dropped the patch."""
-        return _scatter_on_grid(self.relevance[:, row, 2:], self.tokens, self.grid)
-
-
-_INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
-
-
-def _check_target(target, C: int, what: str):
-    """What can be said about a target of attention_relevance without the batch size: its form, the range of class indices, finiteness."""
-    if isinstance(target, bool):
-        raise TypeError(f"{what} must be an int class index, an integer tensor [B] or a float tensor [C] / [B, C], got {target!r}")
-    if isinstance(target, int):
-        if not 0 <= target < C:
-            raise ValueError(f"{what} = {target} out of range for {C} classes")
-        return
-    if not torch.is_tensor(target):
-        raise TypeError(f"{what} must be an int class index, an integer tensor [B] or a float tensor [C] / [B, C], got {target!r}")
-    if target.dtype in _INT_DTYPES:
-        if target.dim() != 1:
-            raise ValueError(f"{what}: an integer tensor holds one class index per clip, [B]; got shape {tuple(target.shape)}")
-        if target.numel() and not (0 <= int(target.min()) and int(target.max()) < C):
-            raise ValueError(f"{what} holds a class index out of range for {C} classes")
-    elif target.is_floating_point():
-        if target.dim() not in (1, 2) or target.shape[-1] != C:
-            raise ValueError(f"{what}: a float tensor holds weights on the {C} logits, [C] or [B, C]; got shape {tuple(target.shape)}")
-        if not bool(torch.isfinite(target).all()):
-            raise ValueError(f"{what} must be finite")
-    else:
-        raise TypeError(f"{what} must be an int class index, an integer tensor [B] or a float tensor [C] / [B, C], got a {target.dtype} tensor")
-
-
-def _check_target_clips(target, B: int, what: str):
-    if torch.is_tensor(target) and target.dim() == (1 if target.dtype in _INT_DTYPES else 2) and target.shape[0] != B:
-        raise ValueError(f"{what} has shape {tuple(target.shape)}: this forward has B = {B} clips")
-
-
-def _target_seed(target, B: int, C: int, what: str, dev, grad_scale: float) -> torch.Tensor:
-    """grad_scale * d(sum(target * logits)) / d logits: fp32 [B, C] on the device."""
-    _check_target_clips(target, B, what)
-    if isinstance(target, int) or target.dtype in _INT_DTYPES:
-        idx = torch.full((B,), target, dtype=torch.long) if isinstance(target, int) else target.detach().cpu().long()
-        seed = torch.zeros((B, C), dtype=torch.float32)
-        seed[torch.arange(B), idx] = grad_scale
-        return seed.to(dev)
-    seed = target.detach().to(device=dev, dtype=torch.float32) * grad_scale
-    return (seed.unsqueeze(0).expand(B, -1) if seed.dim() == 1 else seed).contiguous()
+        return explain.attention_relevance(self, x, target, start, blocks, melspectrogram_input, target_dist=target_dist, grad_scale=grad_scale,
+                                           _patchout=_patchout)
 
 
 # --------------------------------------------------------------------------------------
@@ -1935,3 +1646,8 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
             state_dict = {k: v for k, v in state_dict.items() if "head" not in k}
         model.load_state_dict(state_dict, strict=False)
     return model
+
+
+from . import explain  # noqa: E402  (attention maps, rollout, relevance: a module of their own, which reads the names above)
+from .explain import (AttentionMaps, AttentionRelevance, AttentionRollout, _INT_DTYPES, _check_target, _check_target_clips,  # noqa: E402, F401
+                      _scatter_on_grid, _target_seed)
