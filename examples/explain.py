@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Which time columns make the model say a label: gradient-weighted attention rollout (MAEST.attention_relevance) for the top
-predictions of a clip (random noise unless --wav-npy points at a float32 mono 16 kHz array).
+predictions of a clip (random noise unless --wav-npy points at a float32 mono 16 kHz array), and which heads of which blocks carry the
+evidence for the first of them (MAEST.attention_heads).
 
     python examples/explain.py --seconds 30 [--label "Rock---Shoegaze"] [--checkpoint model.ckpt]"""
 import argparse
@@ -39,6 +40,13 @@ def main():
         best = torch.topk(per_t, 5).indices.tolist()
         print(f"{activations[c]:.3f}  {labels[c]}: top time columns of chunk 0 (of {r.grid[1]}; 0.16 s apart): "
               + ", ".join(f"t={t} ({per_t[t].item():.2e})" for t in best))
+    # which heads carry the evidence for the first of them: the same walk, every block's step kept per head (MAEST.attention_heads)
+    c = wanted[0]
+    h = model.attention_heads(audio, int(c), grad_scale=scale)
+    scores = h.head_scores(row=0)[0]                                     # cls row of chunk 0: [blocks, 12]
+    top = torch.topk(scores.flatten(), 5)
+    print(f"{labels[c]}: heads that pass on the most relevance in chunk 0: "
+          + ", ".join(f"block {i // 12} head {i % 12} ({v:.2e})" for v, i in zip(top.values.tolist(), top.indices.tolist())))
 
 
 if __name__ == "__main__":

@@ -334,6 +334,18 @@ int maest_attn_bwd(const void* qkv, const void* out, const void* dout, const flo
  * in the order and with the single writer of the plain form: two calls are bit-identical.  p, g, W and the sums are fp32 in every mode;
  * q k^T and dO V^T take the mode's arithmetic. */
 #define MAEST_ATTN_APPLY_GRAD 0x800
+/* PER-HEAD POOLING (which heads carry the pooled attention, or the evidence for a label).  MAEST_ATTN_APPLY_HEADS, valid only together
+ * with MAEST_ATTN_APPLY, with or without MAEST_ATTN_APPLY_GRAD (alone, or with MAEST_ATTN_PROBS*: MAEST_ERR_INVALID; base codes those of
+ * the plain form, MAEST_F32X3_A3: MAEST_ERR_INVALID), keeps the twelve heads of the pooling apart instead of averaging them:
+ *   dqkv  = Y, fp32 [B, 12, R, N], contiguous, 16-byte aligned: the call writes exactly these elements.
+ *   dout = W, delta = the lse2 workspace [B, 12, N], out (dO under MAEST_ATTN_APPLY_GRAD, else NULL), lse = NULL, q_rows and the tails
+ *           that may hold anything keep the meaning and the shapes they have without the flag.
+ *   Y[b, h, r, k] = s_h, with s_h exactly the per-head term defined above for the plain form and, under MAEST_ATTN_APPLY_GRAD, for the
+ *           gradient-weighted form: no sum over the heads and no 1 / 12.
+ * IDENTITY: fp32(1 / 12) * (((Y[b, 0] + Y[b, 1]) + Y[b, 2]) + ... + Y[b, 11]), evaluated in fp32 (every add and the product rounded once,
+ * in this order), is BIT-IDENTICAL to what the same call without the flag writes: per head both forms run the same arithmetic in the same
+ * order.  One writer per element, no atomics: two calls are bit-identical. */
+#define MAEST_ATTN_APPLY_HEADS 0x1000
 int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B, int N, int dtype, float scale, int q_rows,
                         void* stream);
 int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

@@ -526,6 +526,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_probs_kernel
 //             staged beside the Q tiles (rows >= q_rows as zero, never read from memory), the V row of the lane's key rides as fragments beside
 //             its K row; g = dO V^T in the mode's arithmetic, a = max(p * g, 0), acc[r] = fma(W[r][q], a, acc[r]).  Everything else -- launch 1,
 //             the order of every sum, one writer per element -- is the plain form's.
+//   HEADS (MAEST_ATTN_APPLY_HEADS, with or without GRAD): launch 2 keeps the heads apart, Y[b, head, r, k] = s_head.  One workgroup per
+//             (clip, head, 128-key block) -- twelve times the grid, a walk one twelfth as long (the query tiles of its one head; the K / V
+//             fragments are loaded once) -- remapped so that the key blocks of one (clip, head), which re-read the same Q / dO tiles and
+//             lse2 row, are neighbours on one L2 (attn_block).  Per head it is the very arithmetic of the mean form: the same fragments, the
+//             same mma_rows, the same FMA chain over the queries, the same half-wave add; only the ascending head sum and the 1 / 12 are
+//             left to the caller, so fp32(1 / 12) * (((Y_0 + Y_1) + Y_2) + ... + Y_11) has the mean form's bits.
 template <typename T, bool X3>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_stats_kernel(const T* __restrict__ qkv, float* __restrict__ lse2,
                                                                                         int B, int N, float sc_c2, int q_rows) {
@@ -599,7 +605,7 @@ __device__ __forceinline__ void apply_side_store(const ApplySide<RP>& sd, char* 
     }
 }
 
-template <typename T, bool X3, int RP, bool GRAD>
+template <typename T, bool X3, int RP, bool GRAD, bool HEADS = false>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                                                   const float* __restrict__ w, const float* __restrict__ lse2,
                                                                                   float* __restrict__ y, int B, int N, float sc_c2, int q_rows,
@@ -613,8 +619,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5;
     const int nkb = (N + 127) / 128;
-    const int wg = xcd_remap(blockIdx.x, nkb * B);
-    const int b = wg / nkb, key0 = (wg % nkb) * 128 + wave * 32;
+    // HEADS: (clip, head, key block), the key blocks of one (clip, head) adjacent; else (clip, key block) and every head in turn
+    const int wg = xcd_remap(blockIdx.x, nkb * (HEADS ? NHEADS : 1) * B);
+    const int b = wg / (nkb * (HEADS ? NHEADS : 1)), key0 = (wg % nkb) * 128 + wave * 32;
+    const int head0 = HEADS ? (wg / nkb) % NHEADS : 0;            // the first head of the walk: HEADS walks this one alone
     const int key = key0 + (lane & 31);
     const bool wave_active = key0 < N;                            // wave-uniform; the other waves only help staging the Q tiles
     const T* qbase = qkv + (int64_t)b * N * QKV_LD;
@@ -625,7 +633,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
     const float* lse2_clip = lse2 + (int64_t)b * NHEADS * N;
 
     const int nqt = (q_rows + 63) / 64;
-    const int nsteps = NHEADS * nqt;                              // (head, query tile), double-buffered across all of them
+    const int nsteps = (HEADS ? 1 : NHEADS) * nqt;                // (head, query tile), double-buffered across all of them
     const float c2 = sc_c2;
     chunk16 kf[C::STEPS], vf[C::STEPS];
     float acc[RP], tot[RP];
@@ -633,14 +641,14 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
     for (int r = 0; r < RP; ++r) { acc[r] = 0.0f; tot[r] = 0.0f; }
     TileRegs<T> qr, dor;
     Side sd;
-    tile_load<T>(qr, qbase, QKV_LD, 0, q_rows, tid);              // (rows >= q_rows read as zero)
-    if constexpr (GRAD) tile_load<T>(dor, dobase, OUT_LD, 0, q_rows, tid);
-    apply_side_load<RP>(sd, w_clip, lse2_clip, N, R, 0, q_rows, tid);
+    tile_load<T>(qr, qbase + head0 * HD, QKV_LD, 0, q_rows, tid);  // (rows >= q_rows read as zero)
+    if constexpr (GRAD) tile_load<T>(dor, dobase + head0 * HD, OUT_LD, 0, q_rows, tid);
+    apply_side_load<RP>(sd, w_clip, lse2_clip + (int64_t)head0 * N, N, R, 0, q_rows, tid);
     tile_store_rows<T>(qr, smem, tid);
     if constexpr (GRAD) tile_store_rows<T>(dor, smem + DO_OFF, tid);
     apply_side_store<RP>(sd, smem + SIDE_OFF, tid);
     __syncthreads();
-    int hh = 0, qt = 0;
+    int hh = head0, qt = 0;
     for (int it = 0; it < nsteps; ++it) {
         const char* q_lds = smem + (it & 1) * C::TILE;
         const char* do_lds = smem + DO_OFF + (it & 1) * C::TILE;
@@ -699,7 +707,7 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
                     const float sh = acc[r] + __shfl_xor(acc[r], 32, 64);
-                    tot[r] = hh == 0 ? sh : tot[r] + sh;
+                    tot[r] = HEADS || hh == 0 ? sh : tot[r] + sh;
                 }
             }
         }
@@ -713,8 +721,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void attn_apply_kernel
     }
     if (wave_active && h == 0 && key < N) {
 #pragma unroll
-        for (int r = 0; r < RP; ++r)
-            if (r < R) y[((int64_t)b * R + r) * N + key] = tot[r] * (1.0f / 12.0f);
+        for (int r = 0; r < RP; ++r) {
+            if constexpr (HEADS) {
+                if (r < R) y[(((int64_t)b * NHEADS + head0) * R + r) * N + key] = tot[r];
+            } else {
+                if (r < R) y[((int64_t)b * R + r) * N + key] = tot[r] * (1.0f / 12.0f);
+            }
+        }
     }
 }
 
@@ -2095,36 +2108,41 @@ static int attn_probs_launch(const void* qkv, void* out, int B, int N, AttnScale
     return check_launch("maest_attn_fwd(probabilities)");
 }
 
-template <typename T, bool X3, int RP, bool GRAD>
+template <typename T, bool X3, int RP, bool GRAD, bool HEADS>
 static void attn_apply_launch_rows(const void* qkv, const void* dout, const float* w, const float* lse2, float* y, int B, int N, float c2,
                                    int q_rows, int R, hipStream_t st) {
     using C = AttnCfg<T>;
     const int smem_bytes = (GRAD ? 4 : 2) * C::TILE + 2 * ApplySide<RP>::FLOATS * 4;
     static DeviceOnce once;
-    ensure_dynamic_lds(once, &attn_apply_kernel<T, X3, RP, GRAD>, smem_bytes);
-    hipLaunchKernelGGL((attn_apply_kernel<T, X3, RP, GRAD>), dim3(((N + 127) / 128) * B), dim3(256), smem_bytes, st, (const T*)qkv,
+    ensure_dynamic_lds(once, &attn_apply_kernel<T, X3, RP, GRAD, HEADS>, smem_bytes);
+    hipLaunchKernelGGL((attn_apply_kernel<T, X3, RP, GRAD, HEADS>), dim3(((N + 127) / 128) * (HEADS ? NHEADS : 1) * B), dim3(256), smem_bytes, st, (const T*)qkv,
                        (const T*)dout, w, lse2, y, B, N, c2, q_rows, R);
 }
-template <typename T, bool X3, bool GRAD>
+template <typename T, bool X3, bool GRAD, bool HEADS>
 static void attn_apply_launch_form(const void* qkv, const void* dout, const float* w, const float* lse2, float* y, int B, int N, float c2,
                                    int q_rows, int R, hipStream_t st) {
-    if (R <= 2) attn_apply_launch_rows<T, X3, 2, GRAD>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
-    else if (R <= 4) attn_apply_launch_rows<T, X3, 4, GRAD>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
-    else attn_apply_launch_rows<T, X3, 8, GRAD>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
+    if (R <= 2) attn_apply_launch_rows<T, X3, 2, GRAD, HEADS>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
+    else if (R <= 4) attn_apply_launch_rows<T, X3, 4, GRAD, HEADS>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
+    else attn_apply_launch_rows<T, X3, 8, GRAD, HEADS>(qkv, dout, w, lse2, y, B, N, c2, q_rows, R, st);
 }
 
 // MAEST_ATTN_APPLY: w fp32 [B, R, N], lse2 fp32 [B, 12, N] (workspace: written by the first launch, read by the second), y fp32 [B, R, N];
-// dout (MAEST_ATTN_APPLY_GRAD; nullptr: the plain form): dO, [B * N, 768] of the operand type
+// dout (MAEST_ATTN_APPLY_GRAD; nullptr: the plain form): dO, [B * N, 768] of the operand type; heads (MAEST_ATTN_APPLY_HEADS): y fp32 [B, 12, R, N]
 template <typename T, bool X3 = false>
 static int attn_apply_launch(const void* qkv, const void* dout, const float* w, float* lse2, float* y, int B, int N, AttnScale sc, int q_rows,
-                             int R, hipStream_t st) {
+                             int R, bool heads, hipStream_t st) {
     using C = AttnCfg<T>;
     static DeviceOnce once;
     ensure_dynamic_lds(once, &attn_apply_stats_kernel<T, X3>, 2 * C::TILE);
     hipLaunchKernelGGL((attn_apply_stats_kernel<T, X3>), dim3(((q_rows + 127) / 128) * NHEADS * B), dim3(256), 2 * C::TILE, st, (const T*)qkv, lse2,
                        B, N, sc.c2, q_rows);
-    if (dout != nullptr) attn_apply_launch_form<T, X3, true>(qkv, dout, w, lse2, y, B, N, sc.c2, q_rows, R, st);
-    else attn_apply_launch_form<T, X3, false>(qkv, nullptr, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    if (heads) {
+        if (dout != nullptr) attn_apply_launch_form<T, X3, true, true>(qkv, dout, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+        else attn_apply_launch_form<T, X3, false, true>(qkv, nullptr, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+        return check_launch("maest_attn_bwd(apply, per head)");
+    }
+    if (dout != nullptr) attn_apply_launch_form<T, X3, true, false>(qkv, dout, w, lse2, y, B, N, sc.c2, q_rows, R, st);
+    else attn_apply_launch_form<T, X3, false, false>(qkv, nullptr, w, lse2, y, B, N, sc.c2, q_rows, R, st);
     return check_launch("maest_attn_bwd(apply)");
 }
 
@@ -2242,8 +2260,14 @@ extern "C" int maest_attn_fwd(const void* qkv, void* out, float* lse, int B, int
 extern "C" int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse,
                                    float* delta, void* dqkv, int B, int N, int dtype, float scale, int q_rows,
                                    void* stream) {
+    // MAEST_ATTN_APPLY_HEADS is a form of MAEST_ATTN_APPLY alone: not of the backward, and the attention maps belong to maest_attn_fwd_rows
+    MAEST_REQUIRE(!(dtype & MAEST_ATTN_APPLY_HEADS) || !(dtype & (MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN)),
+                  "maest_attn_bwd: MAEST_ATTN_APPLY_HEADS with MAEST_ATTN_PROBS (dtype %d): the per-head form belongs to MAEST_ATTN_APPLY", dtype);
+    MAEST_REQUIRE(!(dtype & MAEST_ATTN_APPLY_HEADS) || (dtype & MAEST_ATTN_APPLY),
+                  "maest_attn_bwd: MAEST_ATTN_APPLY_HEADS without MAEST_ATTN_APPLY (dtype %d)", dtype);
     if (dtype & MAEST_ATTN_APPLY) {     // weighted attention pooling: dout = W, dqkv = Y (fp32 [B, R, N] both), delta = the lse2 workspace
         const int base = dtype & 0xFF, rows = ((dtype >> 16) & 0xFF) + 1;
+        constexpr int FLAGS = MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD | MAEST_ATTN_APPLY_HEADS | 0xFF0000;
         MAEST_REQUIRE(qkv && dout && delta && dqkv, "maest_attn_bwd: null pointer");
         MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_bwd: bad shape B=%d N=%d", B, N);
         MAEST_REQUIRE(q_rows > 0 && q_rows <= N, "maest_attn_bwd_rows: q_rows = %d outside 1..N", q_rows);
@@ -2252,19 +2276,19 @@ extern "C" int maest_attn_bwd_rows(const void* qkv, const void* out, const void*
         MAEST_REQUIRE(lse == nullptr, "maest_attn_bwd: MAEST_ATTN_APPLY reads no out and no lse: pass NULL");
         MAEST_REQUIRE(!grad || out != nullptr, "maest_attn_bwd: null pointer (MAEST_ATTN_APPLY_GRAD reads dO from `out`)");
         MAEST_REQUIRE(base != MAEST_F32X3_A3, "maest_attn_bwd: MAEST_ATTN_APPLY keeps fp32 probabilities: no MAEST_F32X3_A3 form");
-        MAEST_REQUIRE((dtype & ~(0xFF | MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD | 0xFF0000)) == 0 &&
-                          (base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS),
-                      "maest_attn_bwd: bad dtype %d under MAEST_ATTN_APPLY", dtype & ~(MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD | 0xFF0000));
+        MAEST_REQUIRE((dtype & ~(0xFF | FLAGS)) == 0 && (base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS),
+                      "maest_attn_bwd: bad dtype %d under MAEST_ATTN_APPLY", dtype & ~FLAGS);
         MAEST_REQUIRE(rows <= 8, "maest_attn_bwd: MAEST_ATTN_APPLY_ROWS: %d weight rows outside 1..8", rows);
         MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)delta % 16) == 0 && ((uintptr_t)dqkv % 16) == 0 &&
                           ((uintptr_t)out % 16) == 0,
                       "maest_attn_bwd: 16-byte alignment");
         const AttnScale sca = attn_scale(scale, base == MAEST_BF16_QS);
+        const bool heads = (dtype & MAEST_ATTN_APPLY_HEADS) != 0;   // per head: dqkv = Y, fp32 [B, 12, R, N]
         if (base == MAEST_F32X3)
-            return attn_apply_launch<float, true>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
+            return attn_apply_launch<float, true>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, heads, (hipStream_t)stream);
         return base == MAEST_F32
-                   ? attn_apply_launch<float>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream)
-                   : attn_apply_launch<bf16_t>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, (hipStream_t)stream);
+                   ? attn_apply_launch<float>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, heads, (hipStream_t)stream)
+                   : attn_apply_launch<bf16_t>(qkv, out, (const float*)dout, delta, (float*)dqkv, B, N, sca, q_rows, rows, heads, (hipStream_t)stream);
     }
     MAEST_REQUIRE(qkv && dout && lse && delta && dqkv, "maest_attn_bwd: null pointer");
     MAEST_REQUIRE(B > 0 && N > 0, "maest_attn_bwd: bad shape B=%d N=%d", B, N);

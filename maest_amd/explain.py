@@ -1,4 +1,4 @@
-"""What MAEST.attention_maps / attention_rollout / attention_relevance run (their contracts are the docstrings of those methods,
+"""What MAEST.attention_maps / attention_rollout / attention_relevance / attention_heads run (their contracts are the docstrings of those methods,
 maest_amd/maest.py): the argument checks -- all of them before any device work --, one engine forward with a tap on every block's qkv
 tensor, the sweeps over the blocks, and the result classes.  The engine knows nothing of these features: the forward hands a tap
 (i, qkv, mode) behind each qkv GEMM, and the relevance step rides as a tap on the engine's one backward chain."""
@@ -83,6 +83,28 @@ class AttentionRelevance(_Explained):
         """Row `row` of the relevance (start="head": 0 = cls, 1 = dist) over the patch tokens, laid out on the patch grid: [B, F', T'],
         NaN where the forward dropped the patch."""
         return self._on_grid(self.relevance[:, row, 2:])
+
+
+class AttentionHeads(_Explained):
+    """What MAEST.attention_heads returns.  kind: "rollout" (no target) or "relevance".  per_head: {block index: fp32 [B, 12, R, N]}, detached,
+    the swept blocks in ascending order: per_head[l][b, h, r, k] is what head h of block l alone pools from the walk's row r onto key token
+    k -- the term whose mean over the heads is the step of the walk at that block.  result: fp32 [B, R, N], the end of the walk: bit for
+    bit the rollout / the relevance of the same arguments.  logits, features, logits_dist, tokens, grid: of the same forward, as in
+    AttentionMaps."""
+
+    def __init__(self, per_head, result, kind, logits, features, tokens, grid, logits_dist=None):
+        super().__init__(logits, features, tokens, grid, logits_dist)
+        self.per_head, self.result, self.kind = per_head, result, kind
+
+    def head_scores(self, row: int = 0) -> torch.Tensor:
+        """[B, number of swept blocks, 12]: per block (ascending) and head, the sum over the key tokens of per_head[block][:, head, row, :]
+        -- how much of row `row` (start="head": 0 = cls, 1 = dist) that head passes on at that block."""
+        return torch.stack([self.per_head[i][:, :, row, :].sum(dim=-1) for i in sorted(self.per_head)], dim=1)
+
+    def to_grid(self, block: int, head: int, row: int = 0) -> torch.Tensor:
+        """Row `row` of one head of block `block` over the patch tokens, laid out on the patch grid: [B, F', T'], NaN where the forward
+        dropped the patch."""
+        return self._on_grid(self.per_head[block][:, head, row, 2:])
 
 
 def _outputs(outs, kw, grid):
@@ -173,9 +195,15 @@ def _sweep_start(start, head_start, B, N, dev):
     return r.clone() if r.data_ptr() % 16 else r      # (a contiguous slice of a larger tensor: the kernel wants 16-byte aligned operands)
 
 
-def attention_rollout(model, x, start, blocks, alpha, melspectrogram_input, *, _patchout):
+def _check_alpha(alpha):
     if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= float(alpha) <= 1.0:
         raise ValueError(f"alpha must be a number in [0, 1], got {alpha!r}")
+
+
+def _rollout_walk(model, x, start, blocks, alpha, melspectrogram_input, _patchout, per_head=None):
+    """The walk of attention_rollout -> (r, the result classes' closing arguments).  per_head (a dict): every step is pooled head by head
+    (ops.attn_apply_heads), kept there under its block index, and the walk goes on with its mean -- the same bits (ops.heads_mean)."""
+    _check_alpha(alpha)
     head_start, first, last = _check_sweep(model, start, blocks)
     x3, dt, kw, grid, B, N = _resolve_sweep(model, x, melspectrogram_input, _patchout, False, start, head_start)
     kept = {}      # block index -> (qkv, mode), alive until the sweep below has read it
@@ -192,9 +220,19 @@ def attention_rollout(model, x, start, blocks, alpha, melspectrogram_input, *, _
         with model._engine._pass(kw.get("f16")):
             for i in range(last, first - 1, -1):
                 qkv, (_, _, scale, x3m, qs) = kept[i]
-                y = ops.attn_apply(qkv, r, B, N, scale, q_rows=HEAD_TOKENS if head_start and i == last else None, x3=x3m, q_prescaled=qs)
+                q_rows = HEAD_TOKENS if head_start and i == last else None
+                if per_head is None:
+                    y = ops.attn_apply(qkv, r, B, N, scale, q_rows=q_rows, x3=x3m, q_prescaled=qs)
+                else:
+                    per_head[i] = ops.attn_apply_heads(qkv, r, B, N, scale, q_rows=q_rows, x3=x3m, q_prescaled=qs)
+                    y = ops.heads_mean(per_head[i])
                 r = torch.add(r * float(alpha), y, alpha=1.0 - float(alpha))
-    return AttentionRollout(rollout=r, **_outputs(outs, kw, grid))
+    return r, _outputs(outs, kw, grid)
+
+
+def attention_rollout(model, x, start, blocks, alpha, melspectrogram_input, *, _patchout):
+    r, out = _rollout_walk(model, x, start, blocks, alpha, melspectrogram_input, _patchout)
+    return AttentionRollout(rollout=r, **out)
 
 
 _INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
@@ -241,7 +279,9 @@ def _target_seed(target, B: int, C: int, what: str, dev, grad_scale: float) -> t
     return (seed.unsqueeze(0).expand(B, -1) if seed.dim() == 1 else seed).contiguous()
 
 
-def attention_relevance(model, x, target, start, blocks, melspectrogram_input, *, target_dist, grad_scale, _patchout):
+def _relevance_walk(model, x, target, start, blocks, melspectrogram_input, target_dist, grad_scale, _patchout, per_head=None):
+    """The walk of attention_relevance -> (r, the result classes' closing arguments).  per_head (a dict): as in _rollout_walk, with
+    ops.attn_relevance_heads."""
     head_start, first, last = _check_sweep(model, start, blocks)
     C = model.head[1].out_features
     _check_target(target, C, "target")
@@ -274,9 +314,35 @@ def attention_relevance(model, x, target, start, blocks, melspectrogram_input, *
             # behind a head-rows block only the head tokens' queries have a gradient (the other rows of dao are zero or unwritten);
             # a one-hot start reads those two rows at the top of the sweep as well
             q_rows = HEAD_TOKENS if s["tail"] or (head_start and i == last) else None
-            y = ops.attn_relevance(s["qkv"], dao, r, B, N, model.blocks[i].attn.scale, q_rows=q_rows, x3=ctx["x3m"], q_prescaled=ctx["qs"])
+            scale = model.blocks[i].attn.scale
+            if per_head is None:
+                y = ops.attn_relevance(s["qkv"], dao, r, B, N, scale, q_rows=q_rows, x3=ctx["x3m"], q_prescaled=ctx["qs"])
+            else:
+                per_head[i] = ops.attn_relevance_heads(s["qkv"], dao, r, B, N, scale, q_rows=q_rows, x3=ctx["x3m"], q_prescaled=ctx["qs"])
+                y = ops.heads_mean(per_head[i])
             r = torch.add(r, y, alpha=1.0 / float(grad_scale))
 
         # the input-gradient chain of a backward, down to block `first`: no weight gradient, no .grad, no side stream, no sink
         model._engine.backward(ctx, tuple(seeds), weights=False, first=first, tap=step)
-    return AttentionRelevance(relevance=r, **_outputs(outs, kw, grid))
+    return r, _outputs(outs, kw, grid)
+
+
+def attention_relevance(model, x, target, start, blocks, melspectrogram_input, *, target_dist, grad_scale, _patchout):
+    r, out = _relevance_walk(model, x, target, start, blocks, melspectrogram_input, target_dist, grad_scale, _patchout)
+    return AttentionRelevance(relevance=r, **out)
+
+
+def attention_heads(model, x, target, start, blocks, alpha, melspectrogram_input, *, target_dist, grad_scale, _patchout):
+    per_head = {}
+    if target is None:
+        if target_dist is not None:
+            raise ValueError("target_dist needs a target: without one the walk is the rollout, which reads no label")
+        if isinstance(grad_scale, bool) or not isinstance(grad_scale, (int, float)) or float(grad_scale) != 1.0:
+            raise ValueError(f"grad_scale belongs to the walk with a target: without one leave it at its default, got {grad_scale!r}")
+        r, out = _rollout_walk(model, x, start, blocks, alpha, melspectrogram_input, _patchout, per_head)
+    else:
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or float(alpha) != 0.5:
+            raise ValueError(f"alpha belongs to the rollout walk (target=None): with a target leave it at its default, got {alpha!r}")
+        r, out = _relevance_walk(model, x, target, start, blocks, melspectrogram_input, target_dist, grad_scale, _patchout, per_head)
+    return AttentionHeads(per_head={i: per_head[i] for i in sorted(per_head)}, result=r, kind="rollout" if target is None else "relevance",
+                          **out)

@@ -1588,6 +1588,24 @@ class MAEST(nn.Module):
         return explain.attention_relevance(self, x, target, start, blocks, melspectrogram_input, target_dist=target_dist, grad_scale=grad_scale,
                                            _patchout=_patchout)
 
+    def attention_heads(self, x, target=None, start="head", blocks=None, alpha: float = 0.5, melspectrogram_input: bool = False, *,
+                        target_dist=None, grad_scale: float = 1.0, _patchout=None) -> "AttentionHeads":
+        """Which heads carry the walk of ``attention_rollout`` (target=None) or of ``attention_relevance`` (a target): the same walk with
+        the same arguments, checks and outputs, but every swept block's step is pooled head by head,
+
+            per_head[l][b, h] = r_l . P_h of block l    (a target: r_l . max(P_h * dP_h, 0)),    fp32 [B, 12, R, N],
+
+        kept, and the walk goes on with its mean over the heads -- the step the other two methods take, bit for bit, so ``result`` is
+        their ``rollout`` / ``relevance`` (the latter where the backward repeats: deterministic=True).  One ops.attn_apply_heads /
+        ops.attn_relevance_heads per block: no N x N tensor is written, and dP_h is never materialised.
+
+        x, start, blocks: as in ``attention_rollout``.  target=None: alpha as in ``attention_rollout``; target_dist and grad_scale stay at
+        their defaults.  target given: target, target_dist, grad_scale as in ``attention_relevance``; alpha stays at its default
+        (ValueError otherwise: that walk has no alpha).  Returns AttentionHeads: per_head, result, kind, head_scores(row), to_grid(block,
+        head, row).  Memory: that of the walk, and 12 x B * R * N floats per swept block."""
+        return explain.attention_heads(self, x, target, start, blocks, alpha, melspectrogram_input, target_dist=target_dist,
+                                       grad_scale=grad_scale, _patchout=_patchout)
+
 
 # --------------------------------------------------------------------------------------
 # architecture registry + factory (models/maest.py:1151-1388, 1467-1569)
@@ -1649,5 +1667,5 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
 
 
 from . import explain  # noqa: E402  (attention maps, rollout, relevance: a module of their own, which reads the names above)
-from .explain import (AttentionMaps, AttentionRelevance, AttentionRollout, _INT_DTYPES, _check_target, _check_target_clips,  # noqa: E402, F401
+from .explain import (AttentionHeads, AttentionMaps, AttentionRelevance, AttentionRollout, _INT_DTYPES, _check_target, _check_target_clips,  # noqa: E402, F401
                       _scatter_on_grid, _target_seed)

@@ -455,6 +455,62 @@ def attn_relevance(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, B: in
     return y
 
 
+def attn_apply_heads(qkv: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False,
+                     q_prescaled=False) -> torch.Tensor:
+    """attn_apply with the heads kept apart: Y[b, h, r, k] = sum_{q < q_rows} w[b, r, q] * softmax(scale q k^T)[b, h, q, k] -> fp32
+    [B, 12, R, N], per head the very arithmetic of attn_apply, so heads_mean(Y) is attn_apply's result bit for bit.  No N x N tensor is
+    written.  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_HEADS on maest_attn_bwd_rows; the arguments are attn_apply's."""
+    _chk(qkv, w)
+    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    assert qkv.shape == (B * N, 3 * EMBED)
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
+    R = w.shape[1]
+    q_rows = N if q_rows is None else q_rows
+    y = torch.empty((B, HEADS, R, N), dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
+    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.ATTN_APPLY_HEADS | _lib.attn_apply_rows(R)
+    # (work: the score product, formed twice)
+    _timed_call("maest_attn_apply_heads", _attn_flops(B, N, q_rows, 4.0), _p(qkv), None, _p(w), None, _p(lse2), _p(y), B, N, code, scale,
+                q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
+    return y
+
+
+def attn_relevance_heads(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False,
+                         q_prescaled=False) -> torch.Tensor:
+    """attn_relevance with the heads kept apart: Y[b, h, r, k] = sum_{q < q_rows} w[b, r, q] * max(P_h[q, k] * dP_h[q, k], 0) -> fp32
+    [B, 12, R, N]; heads_mean(Y) is attn_relevance's result bit for bit.  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD |
+    MAEST_ATTN_APPLY_HEADS on maest_attn_bwd_rows; the arguments are attn_relevance's."""
+    _chk(qkv, dout, w)
+    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    assert qkv.shape == (B * N, 3 * EMBED)
+    assert dout.dtype == qkv.dtype and dout.shape == (B * N, EMBED), (dout.dtype, tuple(dout.shape))
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
+    R = w.shape[1]
+    q_rows = N if q_rows is None else q_rows
+    y = torch.empty((B, HEADS, R, N), dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
+    code = ((BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.ATTN_APPLY_GRAD | _lib.ATTN_APPLY_HEADS
+            | _lib.attn_apply_rows(R))
+    # (work: the score product, formed twice, and the dP product)
+    _timed_call("maest_attn_relevance_heads", _attn_flops(B, N, q_rows, 6.0), _p(qkv), _p(dout), _p(w), None, _p(lse2), _p(y), B, N, code,
+                scale, q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
+    return y
+
+
+_TWELFTH = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(12.0, dtype=torch.float32))   # fp32(1 / 12), the kernels' constant
+
+
+def heads_mean(y: torch.Tensor) -> torch.Tensor:
+    """The mean over the heads of a per-head pooling, fp32 [B, 12, R, N] -> [B, R, N], in the order of the mean-form kernels:
+    (((y_0 + y_1) + y_2) + ... + y_11) * fp32(1 / 12), every add and the product one correctly rounded fp32 operation -- so on the
+    result of attn_apply_heads / attn_relevance_heads it has the bits of attn_apply / attn_relevance."""
+    assert y.dtype == torch.float32 and y.dim() == 4 and y.shape[1] == HEADS, (y.dtype, tuple(y.shape))
+    tot = y[:, 0] + y[:, 1]
+    for h in range(2, HEADS):
+        tot = tot + y[:, h]
+    return tot * _TWELFTH
+
+
 def attn_bwd_rows_supported(dtype, N: int) -> bool:
     """Whether maest_attn_bwd_rows serves q_rows < N for this shape (the fused bf16 kernel: include/maest_hip.h)."""
     return dtype == torch.bfloat16 and -(-N // 32) + 2 <= 12 and get_option("attn_bwd") in (0, 3)
