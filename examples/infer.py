@@ -33,6 +33,7 @@ def main():
         activations, labels = model.predict_labels(audio)
         maps = model.attention_maps(audio, blocks=-1, heads="mean")     # softmax(q k^T * scale) of the last block, cls / dist rows
         roll = model.attention_rollout(audio)                   # which patches feed cls / dist through all 12 blocks
+        hid = model.hidden_states(audio, pool=("embedding", "time"))    # every block's embedding and time-resolved embedding, one forward
     top = np.argsort(activations)[::-1][:5]
     print("logits", tuple(logits.shape), "embeddings", tuple(embeddings.shape), "block-6 embedding", tuple(emb7.shape))
     for i in top:
@@ -46,6 +47,9 @@ def main():
     per_t = torch.nan_to_num(roll.to_grid(row=0)[0]).sum(0)
     best = torch.topk(per_t, 5).indices.tolist()
     print("cls attention rollout over all blocks, top time patches of chunk 0:", ", ".join(f"t={t} ({per_t[t].item():.4f})" for t in best))
+    # the block sweep of embedding extraction from ONE forward: cat[cls, dist, mean(patches)] of every block, and one time-resolved form
+    print("block-wise embedding norms of chunk 0:", ", ".join(f"{k}: {e[0].norm().item():.2f}" for k, e in hid.embedding.items()))
+    print("block-6 time-resolved embedding", tuple(hid.time[6].shape), "= [chunks, kept time patches, 768]")
 
 
 if __name__ == "__main__":

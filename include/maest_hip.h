@@ -351,7 +351,24 @@ int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B, int N, in
 int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                         int B, int N, int dtype, float scale, int q_rows, void* stream);
 /* Rows of the first n_head tokens of every clip, [clips][n_tok][768] -> compact [clips][n_head][768] (dtype fp32 / bf16),
- * and back: dst rows [0, n_pad) of every clip = the compact rows followed by zeros, rows >= n_pad untouched. */
+ * and back: dst rows [0, n_pad) of every clip = the compact rows followed by zeros, rows >= n_pad untouched.
+ *
+ * GRID POOLS (the hidden states: MAEST.hidden_states, pools "time" / "freq").  MAEST_GATHER_POOLS | MAEST_GATHER_POOLS_T(Tk), ORed into `dtype`
+ * of maest_gather_head_rows, turns the call into one that also pools the patch rows behind the head rows.  The base code must be MAEST_F32
+ * (the operands are fp32 in both builds).  With h = n_head and P = n_tok - h the call needs P > 0, Tk >= 1 and P % Tk == 0; Fk = P / Tk: the
+ * patch rows of a clip are an Fk x Tk grid in frequency-major order, row h + f * Tk + t = (frequency patch f, time patch t).
+ *   src: fp32 [clips][n_tok][768], only read.   dst: fp32 [clips][h + 1 + Fk + Tk][768], contiguous; both 16-byte aligned.
+ *   dst row 0 .. h-1        the head rows of src, copied bit for bit
+ *   dst row h               s / (float)P,   s = (..((0.0f + x[h]) + x[h+1]) + ..) over the patch rows in ascending order: the statement of
+ *                           maest_embed_pool (for h = 2 the first three rows are bit-identical to its output)
+ *   dst row h + 1 + f       (sum_t x[h + f * Tk + t]) / (float)Tk,   t ascending        (the mean over time of frequency patch f)
+ *   dst row h + 1 + Fk + t  (sum_f x[h + f * Tk + t]) / (float)Fk,   f ascending        (the mean over frequency of time patch t)
+ * Every sum starts at 0.0f, its adds are fp32 in the stated order, then one IEEE division; one writer per element, no atomics, no partial
+ * sums combined across lanes: two calls are bit-identical, with and without MAEST_OPT_DETERMINISTIC.  The call writes exactly these elements.
+ * MAEST_ERR_INVALID: a base code other than MAEST_F32 beside the flag, Tk = 0, P % Tk != 0, n_tok == n_head, any other bit of bits 8 .. 15,
+ * a misaligned pointer.  Without the flag the entry point is what it was (Tk bits alone: "bad dtype"). */
+#define MAEST_GATHER_POOLS 0x100
+#define MAEST_GATHER_POOLS_T(t) ((t) << 16)     /* Tk = 1 .. 32767 kept time patches */
 int maest_gather_head_rows(const void* src, int clips, int n_tok, int n_head, int dtype, void* dst, void* stream);
 int maest_scatter_head_rows(const void* src, int clips, int n_tok, int n_head, int n_pad, int dtype, void* dst,
                             void* stream);

@@ -28,6 +28,14 @@ ATTN_APPLY_GRAD = 0x800   # ... with MAEST_ATTN_APPLY: the gradient-weighted for
 ATTN_APPLY_HEADS = 0x1000   # ... with MAEST_ATTN_APPLY (and ..._GRAD): the heads kept apart, dqkv = fp32 [B, 12, R, N] (include/maest_hip.h)
 
 
+GATHER_POOLS = 0x100   # flag bit ORed into the dtype of maest_gather_head_rows: the grid pools of the hidden states (include/maest_hip.h)
+
+
+def gather_pools_t(t: int) -> int:
+    """MAEST_GATHER_POOLS_T(t): the number of kept time patches, Tk = 1 .. 32767, as bits of the dtype argument."""
+    return t << 16
+
+
 def attn_apply_rows(r: int) -> int:
     """MAEST_ATTN_APPLY_ROWS(r): the number of weight rows, R = 1 .. 8, as bits of the dtype argument."""
     return (r - 1) << 16

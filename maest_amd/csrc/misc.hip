@@ -170,6 +170,56 @@ __global__ __launch_bounds__(256) void gather_head_rows_kernel(const T* __restri
         *reinterpret_cast<chunk16*>(reinterpret_cast<char*>(dst) + c * 16) = v;
     }
 }
+// ---- MAEST_GATHER_POOLS (include/maest_hip.h): the head rows of every clip, the mean of its patch rows, and their means along the two axes
+// of the Fk x Tk grid the patch rows form (frequency-major), dst fp32 [clips][n_head + 1 + Fk + Tk][768].  Every output element is ONE
+// thread's chain of fp32 adds from 0.0f in ascending row order and one division: no partial sum crosses a lane, so the result is the
+// header's expression bit for bit.  One 192-thread workgroup per (clip, output row), a thread per column quad (a row is 192 x 16 bytes:
+// every load instruction of a workgroup reads one whole 3 KB row); job 0 copies the head rows and walks all P patch rows (the chain of
+// maest_embed_pool), jobs 1 .. Fk walk the Tk consecutive rows of one frequency patch, the last Tk jobs the Fk rows of one time patch, Tk
+// rows apart.  A clip is read three times, the second and third time out of the caches; no LDS, no accumulator array (Tk reaches 187).
+// Eight independent loads are in flight per thread before the eight dependent adds.
+__device__ __forceinline__ float4 pool_rows(const float4* __restrict__ p, int64_t step, int n) {
+    float4 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    int i = 0;
+    for (; i + 8 <= n; i += 8) {
+        float4 v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = p[(int64_t)(i + j) * step];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w;
+        }
+    }
+    for (; i < n; ++i) {
+        const float4 v = p[(int64_t)i * step];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    return s;
+}
+__global__ __launch_bounds__(192) void gather_pools_kernel(const float* __restrict__ src, int n_tok, int n_head, int Tk,
+                                                           float* __restrict__ dst) {
+    constexpr int QPR = 768 / 4;                         // column quads per row = threads per workgroup
+    const int P = n_tok - n_head, Fk = P / Tk;
+    const int jobs = 1 + Fk + Tk;
+    const int64_t clip = blockIdx.x / jobs;
+    const int job = (int)(blockIdx.x - clip * jobs);     // block-uniform
+    const float4* x = reinterpret_cast<const float4*>(src) + (clip * n_tok + n_head) * QPR + threadIdx.x;   // patch row 0
+    float4* d = reinterpret_cast<float4*>(dst) + clip * (n_head + jobs) * QPR + threadIdx.x;
+    float4 s;
+    float n;
+    if (job == 0) {
+        for (int r = 0; r < n_head; ++r) d[(int64_t)r * QPR] = x[(int64_t)(r - n_head) * QPR];
+        s = pool_rows(x, QPR, P);
+        n = (float)P;
+    } else if (job <= Fk) {
+        s = pool_rows(x + (int64_t)(job - 1) * Tk * QPR, QPR, Tk);
+        n = (float)Tk;
+    } else {
+        s = pool_rows(x + (int64_t)(job - 1 - Fk) * QPR, (int64_t)Tk * QPR, Fk);
+        n = (float)Fk;
+    }
+    d[(int64_t)(n_head + job) * QPR] = make_float4(s.x / n, s.y / n, s.z / n, s.w / n);
+}
 // dst rows [0, n_pad) of every clip: the n_head compact rows, then zeros (dst rows >= n_pad are left alone)
 template <typename T>
 __global__ __launch_bounds__(256) void scatter_head_rows_kernel(const T* __restrict__ src, int n_tok, int n_head, int n_pad,
@@ -556,6 +606,22 @@ extern "C" int maest_gather_head_rows(const void* src, int clips, int n_tok, int
     MAEST_REQUIRE(src && dst, "maest_gather_head_rows: null pointer");
     MAEST_REQUIRE(clips > 0 && n_head > 0 && n_tok >= n_head, "maest_gather_head_rows: bad shape clips=%d n_tok=%d n_head=%d",
                   clips, n_tok, n_head);
+    if (dtype & MAEST_GATHER_POOLS) {      // the grid pools of the hidden states: `dtype` = MAEST_F32 | MAEST_GATHER_POOLS | MAEST_GATHER_POOLS_T(Tk)
+        const int Tk = (int)((unsigned)dtype >> 16);
+        MAEST_REQUIRE((dtype & 0xFE00) == 0, "maest_gather_head_rows: bad dtype 0x%x: unknown flag bits beside MAEST_GATHER_POOLS", dtype);
+        MAEST_REQUIRE((dtype & 0xFF) == MAEST_F32, "maest_gather_head_rows: MAEST_GATHER_POOLS pools fp32 rows: the base code must be MAEST_F32, got %d",
+                      dtype & 0xFF);
+        MAEST_REQUIRE(n_tok > n_head, "maest_gather_head_rows: MAEST_GATHER_POOLS needs patch rows behind the head rows (n_tok=%d n_head=%d)",
+                      n_tok, n_head);
+        MAEST_REQUIRE(Tk >= 1, "maest_gather_head_rows: MAEST_GATHER_POOLS_T(Tk) with Tk = 0");
+        MAEST_REQUIRE((n_tok - n_head) % Tk == 0, "maest_gather_head_rows: the %d patch rows are no Fk x Tk grid at Tk = %d", n_tok - n_head, Tk);
+        MAEST_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "maest_gather_head_rows: MAEST_GATHER_POOLS: src / dst alignment (16 bytes)");
+        const int64_t jobs = 1 + (n_tok - n_head) / Tk + Tk;
+        MAEST_REQUIRE(clips * jobs <= 0x7fffffffLL, "maest_gather_head_rows: MAEST_GATHER_POOLS: %lld workgroups", (long long)(clips * jobs));
+        hipLaunchKernelGGL(gather_pools_kernel, dim3((unsigned)(clips * jobs)), dim3(192), 0, (hipStream_t)stream,
+                           reinterpret_cast<const float*>(src), n_tok, n_head, Tk, reinterpret_cast<float*>(dst));
+        return check_launch("maest_gather_head_rows");
+    }
     MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16, "maest_gather_head_rows: bad dtype %d", dtype);
     const int64_t n = (int64_t)clips * n_head * 768 * (dtype == MAEST_BF16 ? 2 : 4) / 16;
     const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);

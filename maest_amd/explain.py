@@ -112,26 +112,30 @@ def _outputs(outs, kw, grid):
     return dict(logits=outs[0], features=outs[-1], tokens=kw["tok_ft"], grid=grid, logits_dist=outs[1] if len(outs) == 3 else None)
 
 
+def _check_blocks(model, blocks) -> frozenset:
+    """The blocks a per-block output is wanted of: an int, an iterable of ints or None (all); negative indices count from the end."""
+    depth = len(model.blocks)
+    if blocks is None:
+        return frozenset(range(depth))
+    if isinstance(blocks, (bool, str)) or not (isinstance(blocks, int) or hasattr(blocks, "__iter__")):
+        raise TypeError(f"blocks must be an int, an iterable of ints or None, got {blocks!r}")
+    want = [blocks] if isinstance(blocks, int) else list(blocks)
+    for i in want:
+        if isinstance(i, bool) or not isinstance(i, int):
+            raise TypeError(f"blocks must be an int, an iterable of ints or None, got an element {i!r}")
+        if not -depth <= i < depth:
+            raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
+    return frozenset(i % depth for i in want)
+
+
 def attention_maps(model, x, blocks, queries, heads, melspectrogram_input, *, _patchout):
     if queries not in ("head", "all"):
         raise ValueError(f"queries must be 'head' or 'all', got {queries!r}")
     if heads not in ("all", "mean"):
         raise ValueError(f"heads must be 'all' or 'mean', got {heads!r}")
-    depth = len(model.blocks)
-    if blocks is None:
-        want = list(range(depth))
-    else:
-        if isinstance(blocks, (bool, str)) or not (isinstance(blocks, int) or hasattr(blocks, "__iter__")):
-            raise TypeError(f"blocks must be an int, an iterable of ints or None, got {blocks!r}")
-        want = [blocks] if isinstance(blocks, int) else list(blocks)
-        for i in want:
-            if isinstance(i, bool) or not isinstance(i, int):
-                raise TypeError(f"blocks must be an int, an iterable of ints or None, got an element {i!r}")
-            if not -depth <= i < depth:
-                raise ValueError(f"block index {i} out of range for a model of {depth} blocks")
-        want = [i % depth for i in want]
+    want = _check_blocks(model, blocks)
     x3, dt, kw, _, grid = model._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
-    want, maps = frozenset(want), {}
+    maps = {}
     q_rows = HEAD_TOKENS if queries == "head" else None
 
     def tap(i, qkv, mode):

@@ -409,11 +409,15 @@ class _Engine:
 
     def _forward(self, x3: torch.Tensor, dt, *, toffset: int, tok_ft: torch.Tensor, perm, lam, stripes=None,
                  stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, tap=None,
-                 explain: bool = False):
+                 explain: bool = False, tap_x=None, full_last: bool = False):
         """x3: fp32 [B, F, T] on the device; tok_ft: int32 [P, 2] kept patch tokens.  Returns (outputs, ctx).
         x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3").
         tap (maest_amd/explain.py: the attention maps and the rollout): called as tap(i, qkv, (B, N, scale, x3m, qs)) right behind block
         i's qkv GEMM, with what an attention kernel needs to read that tensor; None: exactly the launches below.
+        tap_x (maest_amd/hidden.py: the hidden states): called as tap_x(i, x) with block i's output stream -- fp32 [B * N, 768], which no later
+        launch writes -- as soon as that tensor exists: behind the next block's first LayerNorm pass where that pass carries the fc2 add
+        (`pending`), else behind block i's fc2 GEMM, for the last block of the pass behind the loop (there [B * 2, 768] when that block ran
+        on the head rows); None: exactly the launches below.  full_last: the last block runs complete whatever head_tail says.
         explain (MAEST.attention_relevance, with save): the activations are kept for a backward that updates no weight -- the
         operand copies are cached as an evaluation forward caches them, and no dropout / drop-path is drawn (the step counter stays)."""
         recording = save and not explain      # a forward behind which an optimizer may step
@@ -506,6 +510,7 @@ class _Engine:
                 br = dict(elem_a=(8 * i, pe) if pe > 0 else None, path_a=(8 * i + 1, pp) if pp > 0 else None,
                           elem_h=(8 * i + 2, pe) if pe > 0 else None, elem_m=(8 * i + 3, pe) if pe > 0 else None,
                           path_m=(8 * i + 4, pp) if pp > 0 else None)
+            carried = pending is not None      # this block's norm1 pass completes the previous block's output stream
             if pending is not None and pending_reg is not None:
                 r = ops.drop_add_layernorm_fwd(x, pending, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, B, N, N,
                                                pending_reg[0], pending_reg[1], reg["snap"], save_stats=save)
@@ -520,13 +525,15 @@ class _Engine:
             else:
                 r = ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, ops.SPLIT3 if fast3 else dt, save_stats=save)
                 ln1, mean1, rstd1 = r if save else (r, None, None)
+            if tap_x is not None and carried:
+                tap_x(i - 1, x)
             if fast3:
                 qkv = ops.gemm_nt(ln1, w3[(i, "qkv")], qkv_bias[i], out_dtype=torch.float32, split3=True)
             else:
                 qkv = gemm_nt(ln1, W.get(blk.attn.qkv.weight, dt), qkv_bias[i], out_dtype=dt)
             if tap is not None:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
                 tap(i, qkv, (B, N, scale, x3m, qs))
-            tail = self.head_tail and stop_block < 0 and i == nblocks - 1
+            tail = self.head_tail and not full_last and stop_block < 0 and i == nblocks - 1
             # (training needs the backward kernel that honours the restriction; otherwise the attention stays complete
             # and only the per-token part of the block is restricted)
             q_rows = HEAD_TOKENS if tail and (not save or ops.attn_bwd_rows_supported(dt, N)) else None
@@ -600,6 +607,10 @@ class _Engine:
             else:             # last block of this pass: nothing follows that could carry the add
                 x = gemm_nt(g, W.get(blk.mlp.fc2.weight, dt), blk.mlp.fc2.bias, out_dtype=torch.float32,
                                 epi=ops.EPI_RESIDUAL, aux_in=x1)
+            if tap_x is not None and pending is None and i + 1 < nblocks:
+                tap_x(i, x)
+        if tap_x is not None:
+            tap_x(nblocks - 1, x)
         xb = x.reshape(B, -1, EMBED_DIM)          # [B, N, 768], or [B, 2, 768] behind a restricted last block
         if stop_block >= 0:
             return ops.embed_pool(xb), ctx
@@ -1547,6 +1558,36 @@ class MAEST(nn.Module):
         fp32 tensors.  `return_self_attention=True` of ``forward`` is a different tensor: proj(attn @ v) of one block, pooled."""
         return explain.attention_maps(self, x, blocks, queries, heads, melspectrogram_input, _patchout=_patchout)
 
+    def hidden_states(self, x, blocks=None, pool="embedding", melspectrogram_input: bool = False, *, _patchout=None) -> "HiddenStates":
+        """The output stream of every requested block from ONE forward -- what the HF-AST layout calls output_hidden_states --, pooled
+        into the reference's embedding and along the two axes of the patch grid, next to the outputs of the same forward.
+
+        x: everything ``forward`` accepts (the same rank dispatch, chunking and exceptions, as in ``attention_maps``).  blocks: an int,
+        an iterable of ints or None (all); negative indices count from the end.  pool: "embedding", "time", "freq", "states" or an
+        iterable of them (ValueError otherwise).  For every requested block k, of the stream x_k [B, N, 768] behind that block (no final
+        LayerNorm; the state before block 0 is not offered):
+          "embedding"  fp32 [B, 2304] = cat[x_k[:, 0], x_k[:, 1], mean(x_k[:, 2:], 1)]: what ``forward(x, transformer_block=k)[1]`` returns
+          "time"       fp32 [B, Tk, 768]: per kept time patch the mean of its Fk kept frequency patches
+          "freq"       fp32 [B, Fk, 768]: per kept frequency patch the mean of its Tk kept time patches
+          "states"     fp32 [B, N, 768]: x_k itself, as the forward carries it; the caller owns the tensor, no later launch writes it
+        "time" and "freq" need the kept tokens to be a full Fk x Tk grid in frequency-major order: every structured patchout variant and
+        every eval() forward give one; a train() model with u_patchout > 0 does not (ValueError, before any device work).  Every mean is
+        an fp32 sum from 0.0f in ascending token order and one division (ops.embed_pool; ops.grid_pools: one launch per block writes the
+        embedding and both axis pools): bit-reproducible.
+
+        One forward under no_grad in the model's current mode and precision, run eagerly to its end on the caller's stream (no
+        two-stream split, no HIP-graph replay), recording nothing: no output requires grad, and there are no gradients through this
+        call.  When the last block is not among `blocks`, logits and features are those of ``forward``, bit for bit.  When it is, the
+        last block runs complete instead of on the cls / dist rows only (``_engine.head_tail``), and logits and features are, bit for
+        bit, those of a forward with ``_engine.head_tail = False``.  In the 16-bit modes the stream of a block that is not the last one
+        of the pass gets its fc2 add in the next block's LayerNorm pass, from a 16-bit rounded fc2 output (``_engine.split_add_eval``):
+        states and pools are the forward's own values, and equal ``forward(x, transformer_block=k)`` -- which ends its pass at block k
+        with an fp32 fc2 epilogue -- bit for bit in the fp32 modes, for the last block, and for every block once split_add_eval = 0.
+        Returns HiddenStates: embedding / time / freq / states ({block: tensor}, ascending; empty when not requested), time_index,
+        freq_index, on_time_axis(block), on_freq_axis(block) (NaN rows where the forward dropped the column / row), and logits,
+        features, logits_dist, tokens, grid as in AttentionMaps.  Memory: "states" keeps B * N * 768 floats per requested block."""
+        return hidden.hidden_states(self, x, blocks, pool, melspectrogram_input, _patchout=_patchout)
+
     def attention_rollout(self, x, start="head", blocks=None, alpha: float = 0.5, melspectrogram_input: bool = False, *,
                           _patchout=None) -> "AttentionRollout":
         """Attention rollout (Abnar & Zuidema): which input tokens feed the rows of `start` through the blocks,
@@ -1669,3 +1710,5 @@ def get_maest(arch, pretrained: bool = True, n_classes: int = 400, in_channels: 
 from . import explain  # noqa: E402  (attention maps, rollout, relevance: a module of their own, which reads the names above)
 from .explain import (AttentionHeads, AttentionMaps, AttentionRelevance, AttentionRollout, _INT_DTYPES, _check_target, _check_target_clips,  # noqa: E402, F401
                       _scatter_on_grid, _target_seed)
+from . import hidden  # noqa: E402  (the hidden states: reads the names above and explain's)
+from .hidden import HiddenStates  # noqa: E402, F401

@@ -545,6 +545,23 @@ def gather_head_rows(x: torch.Tensor, clips: int, n_tok: int, n_head: int) -> to
     return out
 
 
+def grid_pools(x: torch.Tensor, Tk: int, n_head: int = 2):
+    """The pools of a token stream whose patch rows are an Fk x Tk grid in frequency-major order: x fp32 [clips, n_tok, 768], n_tok =
+    n_head + Fk * Tk -> (head [clips, n_head, 768], mean [clips, 768], freq [clips, Fk, 768], time [clips, Tk, 768]), views of one
+    fp32 [clips, n_head + 1 + Fk + Tk, 768] tensor: the head rows, the mean of all patch rows (for n_head = 2 the first three rows are
+    embed_pool's [clips, 2304], bit for bit), per frequency patch the mean of its Tk time patches, per time patch the mean of its Fk
+    frequency patches -- every sum fp32 from 0.0f in ascending order, one division.  MAEST_GATHER_POOLS on maest_gather_head_rows."""
+    _chk(x)
+    assert x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == EMBED, (x.dtype, tuple(x.shape))
+    clips, n_tok = int(x.shape[0]), int(x.shape[1])
+    P = n_tok - n_head
+    assert isinstance(Tk, int) and 1 <= Tk < 32768 and n_head >= 1 and P >= 1 and P % Tk == 0, (n_tok, n_head, Tk)
+    Fk = P // Tk
+    out = torch.empty((clips, n_head + 1 + Fk + Tk, EMBED), dtype=torch.float32, device=x.device)
+    call("maest_gather_head_rows", _p(x), clips, n_tok, n_head, F32 | _lib.GATHER_POOLS | _lib.gather_pools_t(Tk), _p(out), _s(x))
+    return out[:, :n_head], out[:, n_head], out[:, n_head + 1:n_head + 1 + Fk], out[:, n_head + 1 + Fk:]
+
+
 def scatter_head_rows(xc: torch.Tensor, clips: int, n_tok: int, n_head: int, n_pad: int) -> torch.Tensor:
     """compact [clips * n_head, 768] -> a [clips * n_tok, 768] buffer whose rows [0, n_pad) of every clip hold the compact
     rows followed by zeros; the other rows are UNINITIALISED (never read by maest_attn_bwd_rows)."""
