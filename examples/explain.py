@@ -1,9 +1,10 @@
 #!/usr/bin/env python
 """Which time columns make the model say a label: gradient-weighted attention rollout (MAEST.attention_relevance) for the top
 predictions of a clip (random noise unless --wav-npy points at a float32 mono 16 kHz array), and which heads of which blocks carry the
-evidence for the first of them (MAEST.attention_heads).
+evidence for the first of them (MAEST.attention_heads).  --faithfulness adds the perturbation test (MAEST.perturbation_curve): for rollout,
+relevance and a random ranking, the area under the label's probability while the highest / the lowest scored patches are removed.
 
-    python examples/explain.py --seconds 30 [--label "Rock---Shoegaze"] [--checkpoint model.ckpt]"""
+    python examples/explain.py --seconds 30 [--label "Rock---Shoegaze"] [--checkpoint model.ckpt] [--faithfulness]"""
 import argparse
 import os
 import sys
@@ -23,6 +24,7 @@ def main():
     ap.add_argument("--checkpoint", default=None, help="Lightning .ckpt with net_swa.* / net.* weights")
     ap.add_argument("--label", default=None, help="a label of the model's list; default: the top three predictions")
     ap.add_argument("--precision", default="auto", choices=["auto", "fp32", "bf16", "bf16x3", "fp16"])
+    ap.add_argument("--faithfulness", action="store_true", help="perturbation curves of rollout, relevance and a random ranking")
     args = ap.parse_args()
 
     model = get_maest(args.arch, pretrained=False, checkpoint=args.checkpoint, precision=args.precision).cuda().eval()
@@ -47,6 +49,16 @@ def main():
     top = torch.topk(scores.flatten(), 5)
     print(f"{labels[c]}: heads that pass on the most relevance in chunk 0: "
           + ", ".join(f"block {i // 12} head {i % 12} ({v:.2e})" for v, i in zip(top.values.tolist(), top.indices.tolist())))
+    if args.faithfulness:
+        # a faithful map: the probability falls fast when its highest scores leave first (small positive area) and slowly when its
+        # lowest do (large negative area); the random ranking is the baseline of both
+        maps = {"rollout": model.attention_rollout(audio), "relevance": model.attention_relevance(audio, int(c), grad_scale=scale),
+                "random": "random"}
+        print(f"{labels[c]}: area under the probability per chunk, patches removed in 10 % steps (positive / negative order)")
+        for name, m in maps.items():
+            pos = model.perturbation_curve(audio, m, int(c), order="positive")
+            neg = model.perturbation_curve(audio, m, int(c), order="negative")
+            print(f"  {name:>9}: " + "  ".join(f"{p:.3f} / {n:.3f}" for p, n in zip(pos.auc.tolist(), neg.auc.tolist())))
 
 
 if __name__ == "__main__":

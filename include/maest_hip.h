@@ -395,6 +395,27 @@ int maest_patch_im2col(const void* x, int x_dtype, int B, int F, int T, const in
 int maest_patch_im2col_strided(const void* x, int x_dtype, int B, int F, int T, int stride_f, int stride_t, const int32_t* perm,
                                const float* lam, const int32_t* tok_ft, int P, const int32_t* t_stripes, int n_t,
                                const int32_t* f_stripes, int n_f, void* out, int dtype, void* stream);
+/* KEPT TOKENS PER CLIP (the perturbation curves: MAEST.forward_tokens, MAEST.perturbation_curve).  MAEST_IM2COL_CLIP_TOKENS, ORed into
+ * `dtype` (the output code) of maest_patch_im2col_strided -- and of maest_patch_im2col, which forwards to it --, gives every clip a table of
+ * its own: the reference's unstructured patchout (u_patchout, models/maest.py:773-780) with a chosen index list per clip.
+ *   tok_ft: int32 [B, P, 2], only read; every clip keeps the same number P of tokens.  With prow = b * P + j (64-bit),
+ *           fw = tok_ft[2 * prow], t = tok_ft[2 * prow + 1], f = fw & ~MAEST_TOK_BLANK.
+ *   out[prow, ky * 16 + kx] = m(b, s_f * f + ky, s_t * t + kx)                                            without mixup,
+ *                           = m(b, ..) * lam[b] + m(perm[b], ..) * (1.0f - lam[b])                        with it: the partner at clip b's (f, t),
+ *     m(c, r, s) = 0.0f where sample (r, s) lies in one of clip c's stripes, else (float)x[c, r, s]: the arithmetic of the shared form,
+ *     element by element, rounded to the output type as there (fp32: stored as is).  x in MAEST_F32 or MAEST_F16, every stride, every
+ *     stripe list, out in MAEST_F32 or MAEST_BF16 (the half build: IEEE half) as without the flag.  All index arithmetic is 64-bit.
+ *   MAEST_TOK_BLANK, a bit of the f word of an entry, honoured under the flag only: out[prow, 0 .. 255] = +0.0 -- all-zero bits in both
+ *     output types --, after mixup and stripes, and NO element of x is read for that row (neither the clip's nor its partner's: the row is
+ *     zero over NaN samples too).  f and t must still be valid positions: the token keeps its positional terms in maest_token_assemble,
+ *     which takes the table with the bit cleared.  A table without blank bits gives what the shared form gives clip by clip, bit for bit.
+ * The call writes exactly out[0 .. B * P * 256).  MAEST_ERR_INVALID: any other bit above bit 7 beside the flag ("unknown flag bits"), a
+ * base code other than MAEST_F32 / MAEST_BF16.  Without the flag the entry point is what it was (any bit above the base code: "bad dtype").
+ * maest_patch_im2col_bwd, HIP-graph replay and the outputs that save activations do not take per-clip tables.
+ * maest_token_assemble needs no flag: called with B = 1, P = B * P and the flattened table it writes every clip's patch rows in (b, j)
+ * order behind one cls and one dist row, with the arithmetic of the [B, 2 + P, 768] call per element (maest_amd/ops.py: token_assemble_clips). */
+#define MAEST_IM2COL_CLIP_TOKENS 0x100
+#define MAEST_TOK_BLANK 0x40000000
 
 /* Backward of maest_patch_im2col_strided (ABI 9): the gradient w.r.t. its input x, for a loss that reaches the mel input
  * through the patch-embedding convolution (autograd of PatchEmbed.forward, models/maest.py:243-256, with the mixup of

@@ -29,6 +29,8 @@ ATTN_APPLY_HEADS = 0x1000   # ... with MAEST_ATTN_APPLY (and ..._GRAD): the head
 
 
 GATHER_POOLS = 0x100   # flag bit ORed into the dtype of maest_gather_head_rows: the grid pools of the hidden states (include/maest_hip.h)
+IM2COL_CLIP_TOKENS = 0x100   # flag bit ORed into the dtype of maest_patch_im2col(_strided): tok_ft is [B, P, 2], a table per clip (include/maest_hip.h)
+TOK_BLANK = 0x40000000       # ... a bit of an entry's f word under that flag: the operand row is written as zeros and x is not read
 
 
 def gather_pools_t(t: int) -> int:

@@ -106,6 +106,76 @@ __global__ __launch_bounds__(256) void patch_im2col_kernel(const XT* __restrict_
     }
 }
 
+// MAEST_IM2COL_CLIP_TOKENS (include/maest_hip.h): the same operand with a table of kept tokens PER CLIP, tok_ft int32 [B, P, 2] -- output
+// row prow = b * P + j reads entry prow, and the mixup partner of clip b is read at clip b's positions.  An entry whose f word carries
+// MAEST_TOK_BLANK writes 16 x +0.0 and issues no load of x (nor of lam, perm, the stripes): the row is zero whatever x holds, NaN
+// included, after mixup and stripes.  A kernel of its own, not a template parameter of the one above: that one keeps its name, its arguments and
+// its code.  Same thread mapping (one thread = one (patch row, ky)), same arithmetic per element, 64-bit indices throughout.
+template <typename XT>
+__global__ __launch_bounds__(256) void patch_im2col_clips_kernel(const XT* __restrict__ x, int B, int F, int T,
+                                                                 const int32_t* __restrict__ perm,
+                                                                 const float* __restrict__ lam,
+                                                                 const int32_t* __restrict__ tok_ft, int P,
+                                                                 const int32_t* __restrict__ t_stripes, int n_t,
+                                                                 const int32_t* __restrict__ f_stripes, int n_f,
+                                                                 void* __restrict__ out, int dtype, int stride_f, int stride_t) {
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)B * P * PE_K;
+    if (gid >= total) return;
+    const int ky = (int)(gid & 15);
+    const int64_t prow = gid >> 4;
+    const int b = (int)(prow / P);
+    const int fword = tok_ft[2 * prow];
+    const int64_t o = prow * 256 + ky * 16;
+    float v[16];
+    if (fword & MAEST_TOK_BLANK) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = 0.0f;
+    } else {
+        const int tcol = tok_ft[2 * prow + 1] * stride_t;
+        const int frow = fword * stride_f + ky;
+        const bool masked = n_t + n_f > 0;
+        const XT* src = x + ((int64_t)b * F + frow) * T + tcol;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v[i] = (float)src[i];
+        if (masked) {
+            const uint32_t bits = stripe_bits(t_stripes, n_t, f_stripes, n_f, b, frow, tcol);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = (bits >> i) & 1u ? 0.0f : v[i];
+        }
+        if (lam != nullptr) {
+            const float l = lam[b];
+            const int b2 = perm[b];
+            const XT* src2 = x + ((int64_t)b2 * F + frow) * T + tcol;
+            float u[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) u[i] = (float)src2[i];
+            if (masked) {
+                const uint32_t bits = stripe_bits(t_stripes, n_t, f_stripes, n_f, b2, frow, tcol);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) u[i] = (bits >> i) & 1u ? 0.0f : u[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = v[i] * l + u[i] * (1.0f - l);
+        }
+    }
+    if (dtype == MAEST_BF16) {
+        chunk16* dst = reinterpret_cast<chunk16*>(reinterpret_cast<bf16_t*>(out) + o);
+        chunk16 c0, c1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            c0[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
+            c1[i] = pack_bf2(v[8 + 2 * i], v[8 + 2 * i + 1]);
+        }
+        dst[0] = c0;
+        dst[1] = c1;
+    } else {
+        float4* dst = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + o);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+    }
+}
+
 // x0[b, n, :]: a workgroup owns ONE token position n and a chunk of the batch.  The positional terms of that
 // position (column tcol of time_pos [768, Tt], column f of freq_pos [768, Fg]: strided gathers) are fetched
 // once per workgroup; the batch loop then streams float4 rows (the gather per element had made this kernel
@@ -450,12 +520,28 @@ extern "C" int maest_patch_im2col_strided(const void* x, int x_dtype, int B, int
     MAEST_REQUIRE(F >= PE_K && T >= PE_K, "maest_patch_im2col: input %dx%d smaller than a patch", F, T);
     MAEST_REQUIRE(stride_f > 0 && stride_t > 0, "maest_patch_im2col: bad patch stride (%d, %d)", stride_f, stride_t);
     MAEST_REQUIRE((perm == nullptr) == (lam == nullptr), "maest_patch_im2col: perm and lam go together");
+    const bool clips = (dtype & MAEST_IM2COL_CLIP_TOKENS) != 0;      // tok_ft is [B, P, 2]: `dtype` = base code | MAEST_IM2COL_CLIP_TOKENS
+    if (clips) {
+        MAEST_REQUIRE((dtype & ~0xFF & ~MAEST_IM2COL_CLIP_TOKENS) == 0,
+                      "maest_patch_im2col: bad dtype 0x%x: unknown flag bits beside MAEST_IM2COL_CLIP_TOKENS", dtype);
+        dtype &= 0xFF;
+    }
     MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16, "maest_patch_im2col: bad dtype");
     MAEST_REQUIRE(x_dtype == MAEST_F32 || x_dtype == MAEST_F16, "maest_patch_im2col: input must be fp32 or fp16");
     MAEST_REQUIRE(n_t >= 0 && n_f >= 0 && (n_t == 0 || t_stripes) && (n_f == 0 || f_stripes),
                   "maest_patch_im2col: bad stripe lists");
     const int64_t total = (int64_t)B * P * PE_K;
     const dim3 grid((unsigned)((total + 255) / 256));
+    if (clips) {
+        MAEST_REQUIRE((total + 255) / 256 <= 0x7fffffffLL, "maest_patch_im2col: %lld workgroups", (long long)((total + 255) / 256));
+        if (x_dtype == MAEST_F16)
+            hipLaunchKernelGGL(patch_im2col_clips_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, B,
+                               F, T, perm, lam, tok_ft, P, t_stripes, n_t, f_stripes, n_f, out, dtype, stride_f, stride_t);
+        else
+            hipLaunchKernelGGL(patch_im2col_clips_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)x, B, F,
+                               T, perm, lam, tok_ft, P, t_stripes, n_t, f_stripes, n_f, out, dtype, stride_f, stride_t);
+        return check_launch("maest_patch_im2col");
+    }
     if (x_dtype == MAEST_F16)
         hipLaunchKernelGGL(patch_im2col_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, (const _Float16*)x, B,
                            F, T, perm, lam, tok_ft, P, t_stripes, n_t, f_stripes, n_f, out, dtype, stride_f, stride_t);

@@ -427,7 +427,14 @@ class _Engine:
         x3m = bool(x3m) and dt == torch.float32      # an explicit argument of every product
         gemm_nt = partial(ops.gemm_nt, x3=x3m)
         B, F, T = x3.shape
-        P = int(tok_ft.shape[0])
+        clip_tokens = tok_ft.dim() == 3      # int32 [B, P, 2]: a table per clip (MAEST.forward_tokens; include/maest_hip.h: MAEST_IM2COL_CLIP_TOKENS)
+        if clip_tokens:
+            if save or tap is not None or tap_x is not None or stop_block >= 0:
+                raise ValueError("a table of kept tokens per clip serves forwards that save nothing: no gradients, maps, pools or "
+                                 "intermediate-block outputs (save, tap, tap_x, stop_block)")
+            if tuple(tok_ft.shape[::2]) != (B, 2):
+                raise ValueError(f"tok_ft of shape {tuple(tok_ft.shape)} for a batch of {B} clips: [B, P, 2] wanted")
+        P = int(tok_ft.shape[-2])
         N = 2 + P
         M = B * N
         ctx = {"B": B, "N": N, "toffset": toffset, "tok_ft": tok_ft, "dt": dt, "x3m": x3m, "f16": bool(f16)} if save else None
@@ -475,9 +482,9 @@ class _Engine:
         patches = gemm_nt(cols, W.get(m.patch_embed.proj.weight, dt), m.patch_embed.proj.bias,
                               out_dtype=torch.float32)
         Tt = m.time_new_pos_embed.shape[-1]
-        x = ops.token_assemble(patches, m.cls_token.reshape(-1), m.dist_token.reshape(-1),
-                               m.new_pos_embed.reshape(2, EMBED_DIM), m.freq_new_pos_embed.reshape(EMBED_DIM, -1),
-                               m.time_new_pos_embed.reshape(EMBED_DIM, Tt), toffset, tok_ft, B)
+        x = (ops.token_assemble_clips if clip_tokens else ops.token_assemble)(
+            patches, m.cls_token.reshape(-1), m.dist_token.reshape(-1), m.new_pos_embed.reshape(2, EMBED_DIM),
+            m.freq_new_pos_embed.reshape(EMBED_DIM, -1), m.time_new_pos_embed.reshape(EMBED_DIM, Tt), toffset, tok_ft, B)
         x = x.reshape(M, EMBED_DIM)
         if reg is not None and reg["p"] > 0:       # pos_drop (models/maest.py:800)
             ops.dropout_(x, None, B, N, N, reg["pos_site"], reg["p"], reg["snap"])
@@ -1412,7 +1419,8 @@ class MAEST(nn.Module):
         behind it when this very forward had to rebuild them (they are made on the caller's stream)."""
         eng = self._engine
         B = x3.shape[0]
-        rows = B * (2 + int(kw["tok_ft"].shape[0]))
+        tok = kw["tok_ft"]
+        rows = B * (2 + int(tok.shape[-2]))      # ([P, 2], or a table per clip [B, P, 2]: each half gets its own clips' rows, below)
         if (self.eval_streams < 2 or not x3.is_cuda or B < 2 or rows < self.EVAL_SPLIT_ROWS or kw.get("perm") is not None
                 or kw.get("stripes") is not None or torch.cuda.is_current_stream_capturing()):
             return eng.forward(x3, dt, **kw)[0]
@@ -1423,15 +1431,20 @@ class MAEST(nn.Module):
         start.record(cur)                      # the input (and everything the caller queued before it) is ready
         h = (B + 1) // 2
         xa, xb = x3[:h], x3[h:]
+        kwa = kwb = kw
+        if tok.dim() == 3:
+            kwa, kwb = dict(kw, tok_ft=tok[:h]), dict(kw, tok_ft=tok[h:])
         built = wc.builds
-        outs_a, _ = eng.forward(xa, dt, **kw)
+        outs_a, _ = eng.forward(xa, dt, **kwa)
         if wc.builds != built:
             side.wait_stream(cur)              # cold cache: the copies were made by kernels of the first half's stream
         else:
             side.wait_event(start)
         with torch.cuda.stream(side):
-            outs_b, _ = eng.forward(xb, dt, **kw)
+            outs_b, _ = eng.forward(xb, dt, **kwb)
         xb.record_stream(side)                 # (allocated on the caller's stream, read on the other one)
+        if tok.dim() == 3:
+            tok.record_stream(side)
         cur.wait_stream(side)
         for o in outs_b:
             if o is not None:
@@ -1647,6 +1660,39 @@ class MAEST(nn.Module):
         return explain.attention_heads(self, x, target, start, blocks, alpha, melspectrogram_input, target_dist=target_dist,
                                        grad_scale=grad_scale, _patchout=_patchout)
 
+    def forward_tokens(self, x, keep, blank=None, melspectrogram_input: bool = False, *, _patchout=None):
+        """``forward`` on a chosen set of patch tokens PER CLIP: what ``self(x)`` returns, from one evaluation forward under no_grad (eager, the
+        two-stream split included; no HIP-graph replay, and nothing is recorded).
+
+        x: everything ``forward`` accepts.  keep, blank: bool [B, P] over the call's own token sequence -- what the call resolves before it
+        launches anything: the full patch grid in eval(), with the static patchout variants honoured; P = len of ``tokens`` of the explain
+        methods.  Clip b keeps the tokens where keep[b] is set, in ascending sequence order: the reference's unstructured patchout
+        (u_patchout, models/maest.py:773-780) with a chosen index list per clip; a removed patch is never computed and the attention gets
+        shorter.  Tokens where blank[b] is set stay in the sequence with zeroed content: the convolution's bias plus the positional terms.
+        Every row of keep must hold the same count, at least 1, and blank must be a subset of keep (ValueError; TypeError for masks that
+        are no bool tensors; the value checks cost one device sync).  Gradients, maps, pools and HIP-graph replay on per-clip tokens are
+        not offered."""
+        return perturb.forward_tokens(self, x, keep, blank, melspectrogram_input, _patchout=_patchout)
+
+    def perturbation_curve(self, x, scores, target, order: str = "positive", fractions=None, mode: str = "drop", row: int = 0,
+                           melspectrogram_input: bool = False, *, seed: int = 0, _patchout=None) -> "PerturbationCurve":
+        """The perturbation test of Chefer, Gur & Wolf 2021 (deletion curves, MoRF / LeRF) for a score per patch token: remove a growing
+        fraction of each clip's tokens in the order of its scores and record the target label's probability.  Faithful scores make it
+        fall fast under order="positive" (the highest scores leave first) and slowly under "negative"; scores="random" is the baseline.
+
+        x: everything ``forward`` accepts.  scores: fp32 [B, P] over the call's token sequence (see ``forward_tokens``); or the result of
+        ``attention_rollout`` / ``attention_relevance``, whose [:, row, 2:] is used and whose ``tokens`` must be this call's (ValueError
+        otherwise); or "random": per clip a permutation from a CPU torch.Generator seeded with `seed`.  Non-finite scores: ValueError.
+        Equal scores leave in ascending token index in both orders (a stable sort on the device).  fractions: ascending floats in
+        [0, 1), default (0.0, 0.1, .., 0.9); step k removes r_k = floor(fraction_k * P) tokens of every clip.  mode: "drop" -- the tokens
+        leave the sequence, N_k = 2 + P - r_k -- or "blank" -- they stay with zeroed content (bias plus positions), N constant: the
+        token-level counterpart of zeroing pixels, without the leak the overlap of the 16 x 16 patches at stride 10 would cause.
+        target: a label index, or an integer tensor [B] with one per clip.  Each step is one ``forward_tokens``.  Returns
+        PerturbationCurve: fractions, removed [S], logits [S, B, C], logits_dist, logit and prob [S, B], auc [B], order, mode, tokens,
+        keep_mask(step)."""
+        return perturb.perturbation_curve(self, x, scores, target, order, fractions, mode, row, melspectrogram_input, seed=seed,
+                                          _patchout=_patchout)
+
 
 # --------------------------------------------------------------------------------------
 # architecture registry + factory (models/maest.py:1151-1388, 1467-1569)
@@ -1712,3 +1758,5 @@ from .explain import (AttentionHeads, AttentionMaps, AttentionRelevance, Attenti
                       _scatter_on_grid, _target_seed)
 from . import hidden  # noqa: E402  (the hidden states: reads the names above and explain's)
 from .hidden import HiddenStates  # noqa: E402, F401
+from . import perturb  # noqa: E402  (per-clip token removal and the perturbation curves: reads explain's names)
+from .perturb import PerturbationCurve  # noqa: E402, F401

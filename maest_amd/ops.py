@@ -576,11 +576,16 @@ def patch_im2col(x: torch.Tensor, tok_ft: torch.Tensor, dtype, perm=None, lam=No
     """x fp32 or fp16 [B, F, T], tok_ft int32 [P, 2] -> im2col operand [B*P, 256] (SpecMasking stripes, mixup and
     patchout fused; a float16 batch -- what the reference's loader hands out, discogs/dataset.py:58-67 -- is widened in
     the load).  t_stripes / f_stripes: int32 [B, n, 2] = (start, width) per clip, or None.  stride: (frequency, time) step of the
-    16 x 16 patches (models/maest.py:214-241)."""
+    16 x 16 patches (models/maest.py:214-241).  A 3-D tok_ft, int32 [B, P, 2], is a table per clip (MAEST_IM2COL_CLIP_TOKENS): row
+    b * P + j reads entry (b, j), and an entry whose f word carries _lib.TOK_BLANK gives a row of zeros for which x is not read."""
     _chk(x, tok_ft, perm, lam, t_stripes, f_stripes)
     assert x.dtype in (torch.float32, torch.float16) and x.dim() == 3 and tok_ft.dtype == torch.int32
     B, F, T = x.shape
-    P = tok_ft.shape[0]
+    flag = 0
+    if tok_ft.dim() == 3:
+        assert tok_ft.shape[0] == B and tok_ft.shape[2] == 2, (tuple(tok_ft.shape), B)
+        flag = _lib.IM2COL_CLIP_TOKENS
+    P = tok_ft.shape[-2]
     n_t = n_f = 0
     if t_stripes is not None:
         assert t_stripes.dtype == torch.int32 and t_stripes.dim() == 3 and t_stripes.shape[0] == B and t_stripes.shape[2] == 2
@@ -590,7 +595,7 @@ def patch_im2col(x: torch.Tensor, tok_ft: torch.Tensor, dtype, perm=None, lam=No
         n_f = int(f_stripes.shape[1])
     out = torch.empty((B * P, 256), dtype=dtype, device=x.device)
     call("maest_patch_im2col_strided", _p(x), F16 if x.dtype == torch.float16 else F32, B, F, T, int(stride[0]), int(stride[1]), _p(perm), _p(lam),
-         _p(tok_ft), P, _p(t_stripes) if n_t else None, n_t, _p(f_stripes) if n_f else None, n_f, _p(out), DT[dtype], _s(x))
+         _p(tok_ft), P, _p(t_stripes) if n_t else None, n_t, _p(f_stripes) if n_f else None, n_f, _p(out), DT[dtype] | flag, _s(x))
     return out
 
 
@@ -623,6 +628,18 @@ def token_assemble(patches, cls_token, dist_token, new_pos, freq_pos, time_pos, 
     call("maest_token_assemble", _p(patches), _p(cls_token), _p(dist_token), _p(new_pos), _p(freq_pos),
          _p(time_pos), Fg, Tt, toffset, _p(tok_ft), B, P, _p(x0), _s(patches))
     return x0
+
+
+def token_assemble_clips(patches, cls_token, dist_token, new_pos, freq_pos, time_pos, toffset, tok_ft, B):
+    """token_assemble for a table per clip, tok_ft int32 [B, P, 2] (blank bits allowed: a blank token keeps its positional terms).  One
+    maest_token_assemble call over the B * P patch rows as one clip with the flattened table -- the cls and dist rows once, every patch
+    row with the arithmetic of the [B, 2 + P, 768] call --, then the layout [B, 2 + P, 768] as a torch.cat."""
+    assert tok_ft.dim() == 3 and tok_ft.shape[0] == B and tok_ft.shape[2] == 2 and tok_ft.dtype == torch.int32
+    P = int(tok_ft.shape[1])
+    clear = torch.tensor([~_lib.TOK_BLANK, -1], dtype=torch.int32, device=tok_ft.device)
+    rows = token_assemble(patches, cls_token, dist_token, new_pos, freq_pos, time_pos, toffset,
+                          torch.bitwise_and(tok_ft.reshape(B * P, 2), clear), 1)
+    return torch.cat([rows[:, :2].expand(B, 2, EMBED), rows[0, 2:].reshape(B, P, EMBED)], dim=1)
 
 
 def token_assemble_bwd(dx0, B, Fg, Tt, toffset, tok_ft, dtype, d_cls, d_dist, d_new_pos, d_freq_pos, d_time_pos,
