@@ -346,6 +346,25 @@ int maest_attn_bwd(const void* qkv, const void* out, const void* dout, const flo
  * in this order), is BIT-IDENTICAL to what the same call without the flag writes: per head both forms run the same arithmetic in the same
  * order.  One writer per element, no atomics: two calls are bit-identical. */
 #define MAEST_ATTN_APPLY_HEADS 0x1000
+/* TOKEN COUNTS PER CLIP (ragged batches: MAEST.forward_tokens(ragged=True), MAEST.forward_lengths, perturbation_curve(by="mass")).
+ * MAEST_ATTN_LENS, ORed into `dtype` of maest_attn_fwd_rows / maest_attn_fwd (base codes MAEST_F32, MAEST_F32X3, MAEST_F32X3_A3, MAEST_BF16
+ * -- the half build: IEEE half --, MAEST_BF16_QS), turns the call into an evaluation form in which every clip attends over its own number
+ * of tokens.  Under the flag `lse` is NOT an output: it carries
+ *   n_tok = (const int32_t*) lse, [B], on the device, 4-byte aligned, only read.  NULL: MAEST_ERR_INVALID.  No lse is saved.
+ * Clip b has n_b = n_tok[b] real tokens, 1 <= n_b <= N: rows [0, n_b) of its N-row slab of qkv (the pitch stays N).  Values outside 1..N
+ * are the caller's error (the Python layer checks them; the kernels do not).
+ *   keys >= n_b are not attended, and rows >= n_b of qkv are never read: they may hold anything, NaN included (the tile rows the kernels
+ *           clamp to row N - 1 without the flag are clamped to row n_b - 1).
+ *   out rows q < n_b: softmax attention over the clip's n_b keys -- the key tiles are walked in the order and with the masking of an
+ *           unflagged call at B = 1, N = n_b on those rows: BIT-IDENTICAL to it in every form (and to the unflagged call when n_b = N).
+ *   out rows n_b <= q < N that the call would have written without the flag (q_rows < N: those below roundup(q_rows, 32), as ever) are
+ *           written as zeros (+0.0; under MAEST_F32X3_A3 all three thirds), so that padded rows stay finite and repeatable through the
+ *           per-token kernels behind; rows the unflagged call leaves unwritten stay unwritten.
+ * Work is skipped: a workgroup or wave whose queries are all >= n_b writes its zeros and leaves, and the key loop runs ceil(n_b / 64)
+ * tiles; padded tiles are not loaded.  The cost is sum_b n_b^2, not B N^2.  16-bit operands take the LDS-DMA kernel at every N (the
+ * persistent N > 320 kernel knows no counts); MAEST_OPT_ATTN_FWD = 1 and MAEST_OPT_ATTN_FWD_WAVES keep their meaning.
+ * Together with MAEST_ATTN_PROBS*: MAEST_ERR_INVALID.  maest_attn_bwd(_rows) does not know the flag: MAEST_ERR_INVALID. */
+#define MAEST_ATTN_LENS 0x2000
 int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B, int N, int dtype, float scale, int q_rows,
                         void* stream);
 int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,

@@ -25,6 +25,7 @@ F32X3 = 2   # fp32 tensors, split-bf16 matrix products (maest_gemm_nt in_dtype /
 ATTN_PROBS, ATTN_PROBS_MEAN = 0x100, 0x200   # flag bits ORed into the dtype of maest_attn_fwd(_rows): the attention maps (include/maest_hip.h)
 ATTN_APPLY = 0x400   # flag bit ORed into the dtype of maest_attn_bwd(_rows): weighted attention pooling (include/maest_hip.h)
 ATTN_APPLY_GRAD = 0x800   # ... with MAEST_ATTN_APPLY: the gradient-weighted form, out = dO (include/maest_hip.h)
+ATTN_LENS = 0x2000   # flag bit ORed into the dtype of maest_attn_fwd(_rows): `lse` carries int32 [B] token counts per clip (include/maest_hip.h)
 ATTN_APPLY_HEADS = 0x1000   # ... with MAEST_ATTN_APPLY (and ..._GRAD): the heads kept apart, dqkv = fp32 [B, 12, R, N] (include/maest_hip.h)
 
 

@@ -234,13 +234,39 @@ __device__ __forceinline__ void store_dT_ok(const f32x16_t (&acc)[2], T* row_ptr
     else if (ok) store_dT<T>(acc, row_ptr, lane, mul);
 }
 
+// MAEST_ATTN_LENS: rows [n_tok[b], N) of a clip that the unflagged call would write leave as zeros.
+// a whole 32-query group (wave-uniform call; lane & 31 = row, as store_dT): fp32 / 16-bit rows, or the MAEST_SPLIT3_A thirds
+template <typename T>
+__device__ __forceinline__ void lens_zero_rows(void* out, int b, int N, int q, int head, int lane, bool a3) {
+    f32x16_t z[2];
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) z[db][r] = 0.0f;
+    const bool ok = q < N;
+    if constexpr (sizeof(T) == 4) {
+        if (a3) {
+            store_dT_split3(z, reinterpret_cast<bf16_t*>(out) + ((int64_t)b * N + (ok ? q : 0)) * (3 * OUT_LD) + head * HD, lane, 1.0f, ok);
+            return;
+        }
+    }
+    store_dT_ok<T>(z, reinterpret_cast<T*>(out) + ((int64_t)b * N + q) * OUT_LD + head * HD, lane, 1.0f, ok);
+}
+__device__ __forceinline__ void lens_zero_acc(f32x16_t (&o)[2], bool pad) {
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[db][r] = pad ? 0.0f : o[db][r];
+}
+
 // =================================================================================== forward
-template <typename T, bool X3 = false>
+template <typename T, bool X3 = false, bool LENS = false>
 __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(const T* __restrict__ qkv,
                                                                                 T* __restrict__ out,
                                                                                 float* __restrict__ lse, int B, int N,
                                                                                 float sc_c2, int q_rows, int out_a3) {
     // out_a3 (fp32 operands only): `out` is a bf16 [B * N, 3 * 768] tensor of MAEST_SPLIT3_A rows (hi | hi | lo of the fp32 result)
+    // LENS (MAEST_ATTN_LENS): `lse` carries const int32_t* n_tok [B]; NK = n_tok[b] keys and queries of the clip's N-row slab are real
     using C = AttnCfg<T>;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x { K[key][d], V[key][d] }
 
@@ -250,13 +276,21 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
     if (blk.rb * 128 >= q_rows) return;   // block-uniform: only the first q_rows queries are wanted (the head's tokens)
     const int q0 = blk.rb * 128 + wave * 32;
     const int q = q0 + (lane & 31);
-    const bool wave_active = q0 < N && q0 < q_rows;   // wave-uniform
+    int NK = N;                                       // the clip's real tokens (block-uniform)
+    if constexpr (LENS) {
+        NK = reinterpret_cast<const int*>(lse)[b];
+        if (q0 >= NK) {                               // wave-uniform; from a workgroup's first wave on: all of it, before any barrier
+            if (q0 < N && q0 < q_rows) lens_zero_rows<T>(out, b, N, q, head, lane, sizeof(T) == 4 && out_a3);
+            if (blk.rb * 128 >= NK) return;           // block-uniform: no query of this workgroup is real
+        }
+    }
+    const bool wave_active = q0 < NK && q0 < q_rows;  // wave-uniform
     const T* qbase = qkv + (int64_t)b * N * QKV_LD + head * HD;
     const T* kbase = qbase + NHEADS * HD;
     const T* vbase = qbase + 2 * NHEADS * HD;
 
     chunk16 qf[C::STEPS];
-    row_frags_load<T>(qf, qbase, QKV_LD, q, N, h);
+    row_frags_load<T>(qf, qbase, QKV_LD, q, NK, h);
 
     f32x16_t o[2];
 #pragma unroll
@@ -266,10 +300,10 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
     float m_run = NEG_BIG, l_run = 0.0f;
     const float c2 = sc_c2;
 
-    const int ntiles = (N + 63) / 64;
+    const int ntiles = (NK + 63) / 64;
     TileRegs<T> kr, vr;
-    tile_load<T>(kr, kbase, QKV_LD, 0, N, tid);
-    tile_load<T>(vr, vbase, QKV_LD, 0, N, tid);
+    tile_load<T>(kr, kbase, QKV_LD, 0, NK, tid);
+    tile_load<T>(vr, vbase, QKV_LD, 0, NK, tid);
     tile_store_rows<T>(kr, smem, tid);
     tile_store_rows<T>(vr, smem + C::TILE, tid);
     __syncthreads();
@@ -278,8 +312,8 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
         const char* v_lds = k_lds + C::TILE;
         const bool more = kt + 1 < ntiles;
         if (more) {
-            tile_load<T>(kr, kbase, QKV_LD, (kt + 1) * 64, N, tid);
-            tile_load<T>(vr, vbase, QKV_LD, (kt + 1) * 64, N, tid);
+            tile_load<T>(kr, kbase, QKV_LD, (kt + 1) * 64, NK, tid);
+            tile_load<T>(vr, vbase, QKV_LD, (kt + 1) * 64, NK, tid);
         }
         if (wave_active) {   // waves whose 32 queries are all padding only help staging the tiles
         // S^T[key][q]
@@ -292,12 +326,12 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
         }
         // online softmax in the scaled log2 domain: p = 2^(s*c2 - m).  Only the ragged last tile pays for
         // key masking; the elementwise work is written on float pairs (v_pk_fma_f32 / v_pk_add_f32).
-        if (kt == ntiles - 1 && (N & 63) != 0) {
+        if (kt == ntiles - 1 && (NK & 63) != 0) {
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    if (kt * 64 + kb * 32 + frag_row(r, lane) >= N) s[kb][r] = NEG_BIG;
+                    if (kt * 64 + kb * 32 + frag_row(r, lane) >= NK) s[kb][r] = NEG_BIG;
         }
         float mx = NEG_BIG;
 #pragma unroll
@@ -343,12 +377,13 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 4 : 1) void attn_fwd_kernel(c
         // (staging O through LDS for whole-row stores was measured: no gain at N = 290, -16 % at N = 560;
         // profiles/r03_attn_fwd_ablation.txt.  The 16-byte pieces of store_dT_ok need no LDS and no barrier.)
         const bool ok = q < N;
+        if constexpr (LENS) lens_zero_acc(o, q >= NK);      // the padded rows of a wave with real ones leave as zeros
         if (sizeof(T) == 4 && out_a3) {
             store_dT_split3(o, reinterpret_cast<bf16_t*>(out) + ((int64_t)b * N + (ok ? q : 0)) * (3 * OUT_LD) + head * HD, lane, inv, ok);
         } else {
             store_dT_ok<T>(o, out + ((int64_t)b * N + q) * OUT_LD + head * HD, lane, inv, ok);
         }
-        if (ok && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
+        if (!LENS && ok && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
     }
 }
 
@@ -1045,7 +1080,7 @@ constexpr int RING = 2;       // ring depth of the K / V tiles: one tile ahead (
 // breaks even where the padding is equal (N = 1685: 756 against 767 us).  The refills are latency the four co-resident
 // workgroups already hide, not bandwidth.  Only N <= 256 with more than 128 rows gains (N = 129: 56 against 65 us).
 // attn_fwd_waves() therefore keeps NW = 4; MAEST_OPT_ATTN_FWD_WAVES forces another for tests and A/B.
-template <int NW>
+template <int NW, bool LENS = false>
 __global__ __launch_bounds__(NW * 64, 16 / NW) void attn_fwd_dma_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                               float* __restrict__ lse, int B, int N, float sc_c2, int q_rows) {
     using T = bf16_t;
@@ -1061,31 +1096,39 @@ __global__ __launch_bounds__(NW * 64, 16 / NW) void attn_fwd_dma_kernel(const bf
     if (blk.rb * QB >= q_rows) return;    // block-uniform: only the first q_rows queries are wanted (the head's tokens)
     const int q0 = blk.rb * QB + wave * 32;
     const int q = q0 + (lane & 31);
-    const bool wave_active = q0 < N && q0 < q_rows;   // wave-uniform
+    int NK = N;                                       // the clip's real tokens (block-uniform)
+    if constexpr (LENS) {                             // MAEST_ATTN_LENS: `lse` carries const int32_t* n_tok [B]
+        NK = reinterpret_cast<const int*>(lse)[b];
+        if (q0 >= NK) {                               // wave-uniform; from a workgroup's first wave on: all of it, before any barrier
+            if (q0 < N && q0 < q_rows) lens_zero_rows<T>(out, b, N, q, head, lane, false);
+            if (blk.rb * QB >= NK) return;            // block-uniform: no query of this workgroup is real
+        }
+    }
+    const bool wave_active = q0 < NK && q0 < q_rows;  // wave-uniform
     const T* qbase = qkv + (int64_t)b * N * QKV_LD + head * HD;
     const T* kbase = qbase + NHEADS * HD;
     const T* vbase = qbase + 2 * NHEADS * HD;
 
-    const int ntiles = (N + 63) / 64;
+    const int ntiles = (NK + 63) / 64;
     // this wave's share of the 16 one-KiB pieces (8 of K, 8 of V) of key tile kt -> ring buffer kt % RING.  Pieces 2w, 2w + 1 of
     // K and of V at NW = 4; dealt round-robin otherwise (the waits below are vmcnt(0): the count per wave does not matter)
     auto tile_dma = [&](int kt) {
         char* kb = smem + (kt % RING) * 2 * TILE128;
         if constexpr (NW == 4) {
-            dma_rows128(kb, kbase, QKV_LD, kt * 64, 2 * wave, 2 * wave + 2, 1, N, lane);
-            dma_rows128(kb + TILE128, vbase, QKV_LD, kt * 64, 2 * wave, 2 * wave + 2, 1, N, lane);
+            dma_rows128(kb, kbase, QKV_LD, kt * 64, 2 * wave, 2 * wave + 2, 1, NK, lane);
+            dma_rows128(kb + TILE128, vbase, QKV_LD, kt * 64, 2 * wave, 2 * wave + 2, 1, NK, lane);
         } else {
 #pragma unroll
             for (int p0 = 0; p0 < 16; p0 += NW) {
                 const int p = p0 + wave;
-                if (p < 8) dma_rows128(kb, kbase, QKV_LD, kt * 64, p, p + 1, 1, N, lane);
-                else if (p < 16) dma_rows128(kb + TILE128, vbase, QKV_LD, kt * 64, p - 8, p - 7, 1, N, lane);
+                if (p < 8) dma_rows128(kb, kbase, QKV_LD, kt * 64, p, p + 1, 1, NK, lane);
+                else if (p < 16) dma_rows128(kb + TILE128, vbase, QKV_LD, kt * 64, p - 8, p - 7, 1, NK, lane);
             }
         }
     };
     tile_dma(0);
     chunk16 qf[C::STEPS];
-    row_frags_load<T>(qf, qbase, QKV_LD, q, N, h);
+    row_frags_load<T>(qf, qbase, QKV_LD, q, NK, h);
 
     f32x16_t o[2];
 #pragma unroll
@@ -1109,12 +1152,12 @@ __global__ __launch_bounds__(NW * 64, 16 / NW) void attn_fwd_dma_kernel(const bf
                 for (int r = 0; r < 16; ++r) s[kb][r] = 0.0f;
                 mma_rows_swz(s[kb], k_lds, kb * 32, lane, qf);           // S^T[key][q]
             }
-            if (kt == ntiles - 1 && (N & 63) != 0) {
+            if (kt == ntiles - 1 && (NK & 63) != 0) {
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        if (kt * 64 + kb * 32 + frag_row(r, lane) >= N) s[kb][r] = NEG_BIG;
+                        if (kt * 64 + kb * 32 + frag_row(r, lane) >= NK) s[kb][r] = NEG_BIG;
             }
             float mx = NEG_BIG;
 #pragma unroll
@@ -1153,8 +1196,9 @@ __global__ __launch_bounds__(NW * 64, 16 / NW) void attn_fwd_dma_kernel(const bf
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     if (wave_active) {      // (wave-uniform)
+        if constexpr (LENS) lens_zero_acc(o, q >= NK);      // the padded rows of a wave with real ones leave as zeros
         store_dT_ok<T>(o, out + ((int64_t)b * N + q) * OUT_LD + head * HD, lane, inv, q < N);
-        if (q < N && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
+        if (!LENS && q < N && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
     }
 }
 
@@ -1198,6 +1242,7 @@ __device__ __forceinline__ void x3_tile_store(const X3TileRegs& t, char* hi_tile
         *reinterpret_cast<chunk8*>(lo_tile + off) = lo;
     }
 }
+template <bool LENS = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_x3s_kernel(const float* __restrict__ qkv, void* __restrict__ out, float* __restrict__ lse,
                                                               int B, int N, float sc_c2, int out_a3) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 x { K_hi, K_lo, V_hi, V_lo }: 64 KiB
@@ -1207,19 +1252,27 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3s_kernel(const float* __res
     const int head = blk.head, b = blk.b;
     const int q0 = blk.rb * 128 + wave * 32;
     const int q = q0 + (lane & 31);
-    const bool wave_active = q0 < N;              // wave-uniform
+    int NK = N;                                   // the clip's real tokens (block-uniform)
+    if constexpr (LENS) {                         // MAEST_ATTN_LENS: `lse` carries const int32_t* n_tok [B]
+        NK = reinterpret_cast<const int*>(lse)[b];
+        if (q0 >= NK) {                           // wave-uniform; from a workgroup's first wave on: all of it, before any barrier
+            if (q0 < N) lens_zero_rows<float>(out, b, N, q, head, lane, out_a3 != 0);
+            if (blk.rb * 128 >= NK) return;       // block-uniform: no query of this workgroup is real
+        }
+    }
+    const bool wave_active = q0 < NK;             // wave-uniform
     const float* qbase = qkv + (int64_t)b * N * QKV_LD + head * HD;
     const float* kbase = qbase + NHEADS * HD;
     const float* vbase = qbase + 2 * NHEADS * HD;
 
-    const int ntiles = (N + 63) / 64;
+    const int ntiles = (NK + 63) / 64;
     X3TileRegs kr, vr;
-    x3_tile_load(kr, kbase, 0, N, tid);
-    x3_tile_load(vr, vbase, 0, N, tid);
+    x3_tile_load(kr, kbase, 0, NK, tid);
+    x3_tile_load(vr, vbase, 0, NK, tid);
     // Q: chunk step s of the bf16 layout = d 16 s + 8 h ..+7 of this lane's row, split once
     chunk16 qh[4], ql[4];
     {
-        const float* qp = qbase + (int64_t)(q < N ? q : N - 1) * QKV_LD;
+        const float* qp = qbase + (int64_t)(q < NK ? q : NK - 1) * QKV_LD;
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
             const chunk16 f0 = *reinterpret_cast<const chunk16*>(qp + 16 * st + 8 * h);
@@ -1246,8 +1299,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3s_kernel(const float* __res
         const char *khi = buf, *klo = buf + TILE128, *vhi = buf + 2 * TILE128, *vlo = buf + 3 * TILE128;
         const bool more = kt + 1 < ntiles;
         if (more) {
-            x3_tile_load(kr, kbase, (kt + 1) * 64, N, tid);
-            x3_tile_load(vr, vbase, (kt + 1) * 64, N, tid);
+            x3_tile_load(kr, kbase, (kt + 1) * 64, NK, tid);
+            x3_tile_load(vr, vbase, (kt + 1) * 64, NK, tid);
         }
         if (wave_active) {   // waves whose 32 queries are all padding only help staging the tiles
             // S^T[key][q] = K Q^T: per 16-d chunk step lo*hi, hi*lo, hi*hi
@@ -1267,12 +1320,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3s_kernel(const float* __res
                     mma_chunk<bf16_t>(s[kb], ah, qh[st]);
                 }
             }
-            if (kt == ntiles - 1 && (N & 63) != 0) {
+            if (kt == ntiles - 1 && (NK & 63) != 0) {
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        if (kt * 64 + kb * 32 + frag_row(r, lane) >= N) s[kb][r] = NEG_BIG;
+                        if (kt * 64 + kb * 32 + frag_row(r, lane) >= NK) s[kb][r] = NEG_BIG;
             }
             float mx = NEG_BIG;
 #pragma unroll
@@ -1335,12 +1388,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_x3s_kernel(const float* __res
     const float inv = 1.0f / l_tot;
     if (wave_active) {      // (wave-uniform)
         const bool ok = q < N;
+        if constexpr (LENS) lens_zero_acc(o, q >= NK);      // the padded rows of a wave with real ones leave as zeros
         if (out_a3) {
             store_dT_split3(o, reinterpret_cast<bf16_t*>(out) + ((int64_t)b * N + (ok ? q : 0)) * (3 * OUT_LD) + head * HD, lane, inv, ok);
         } else if (ok) {
             store_dT<float>(o, reinterpret_cast<float*>(out) + ((int64_t)b * N + q) * OUT_LD + head * HD, lane, inv);
         }
-        if (ok && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
+        if (!LENS && ok && lse != nullptr && h == 0) lse[((int64_t)b * NHEADS + head) * N + q] = m_run * LN2 + logf(l_tot);
     }
 }
 
@@ -2049,19 +2103,23 @@ static int attn_fwd_waves(int N, int q_rows) {
 int attn_fwd_pw_launch(const void* qkv, void* out, float* lse, int B, int N, AttnScale sc, bool q_prescaled, hipStream_t st);   // attn_fwd_pw.hip
 bool attn_fwd_pw_available();   // false in a build whose register audit failed (maest_amd/build.py)
 
-template <typename T, bool X3 = false>
+// LENS (MAEST_ATTN_LENS): `lse` carries the clips' token counts, const int32_t [B], and the launch takes the <.., true> instantiations;
+// without it exactly the kernels and arguments of ever.  16-bit operands then take the LDS-DMA form at every N (the persistent kernel
+// knows no counts); MAEST_OPT_ATTN_FWD = 1 keeps forcing the register-staged forms, MAEST_OPT_ATTN_FWD_WAVES the workgroup size.
+template <typename T, bool X3 = false, bool LENS = false>
 static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N, AttnScale sc, bool q_prescaled, int q_rows, hipStream_t st,
                            bool out_a3 = false) {
     using C = AttnCfg<T>;
     if constexpr (sizeof(T) == 2 && !X3) {
         const int afw = option(MAEST_OPT_ATTN_FWD);
         // the long token rows (10 s inference, 30 s shapes): the persistent one-wave-per-SIMD form; 3 forces it at any N (tests)
-        if (q_rows == N && ((afw == 0 && N > 320) || afw == 3) && attn_fwd_pw_available()) return attn_fwd_pw_launch(qkv, out, lse, B, N, sc, q_prescaled, st);
+        if constexpr (!LENS)
+            if (q_rows == N && ((afw == 0 && N > 320) || afw == 3) && attn_fwd_pw_available()) return attn_fwd_pw_launch(qkv, out, lse, B, N, sc, q_prescaled, st);
         if (afw == 0 || afw == 2 || afw == 3) {     // K / V tiles by LDS-DMA (unpadded, swizzled); 2 forces this form at any N
             const int nw = attn_fwd_waves(N, q_rows);
             const dim3 g(((N + nw * 32 - 1) / (nw * 32)) * NHEADS * B);
             const int lds = RING * 2 * 64 * 128;
-#define MAEST_FWD_LAUNCH(NW_) hipLaunchKernelGGL(attn_fwd_dma_kernel<NW_>, g, dim3(NW_ * 64), lds, st, (const bf16_t*)qkv, \
+#define MAEST_FWD_LAUNCH(NW_) hipLaunchKernelGGL((attn_fwd_dma_kernel<NW_, LENS>), g, dim3(NW_ * 64), lds, st, (const bf16_t*)qkv, \
                                                  (bf16_t*)out, lse, B, N, sc.c2, q_rows)
             if (nw == 5) MAEST_FWD_LAUNCH(5);
             else if (nw == 6) MAEST_FWD_LAUNCH(6);
@@ -2076,16 +2134,16 @@ static int attn_fwd_launch(const void* qkv, void* out, float* lse, int B, int N,
         // split-bf16, complete passes: the kernel on pre-split tiles (MAEST_OPT_ATTN_FWD = 1 keeps the per-use split form: A/B, tests)
         if (q_rows == N && option(MAEST_OPT_ATTN_FWD) != 1) {
             static DeviceOnce once_x;
-            ensure_dynamic_lds(once_x, &attn_fwd_x3s_kernel, 8 * 64 * 128);
-            hipLaunchKernelGGL(attn_fwd_x3s_kernel, dim3(((N + 127) / 128) * NHEADS * B), dim3(256), 8 * 64 * 128, st, (const float*)qkv, out, lse,
+            ensure_dynamic_lds(once_x, &attn_fwd_x3s_kernel<LENS>, 8 * 64 * 128);
+            hipLaunchKernelGGL(attn_fwd_x3s_kernel<LENS>, dim3(((N + 127) / 128) * NHEADS * B), dim3(256), 8 * 64 * 128, st, (const float*)qkv, out, lse,
                                B, N, sc.c2, out_a3 ? 1 : 0);
             return check_launch("maest_attn_fwd(x3, split tiles)");
         }
     }
     const int smem_bytes = 4 * C::TILE;
     static DeviceOnce once;
-    ensure_dynamic_lds(once, &attn_fwd_kernel<T, X3>, smem_bytes);
-    hipLaunchKernelGGL((attn_fwd_kernel<T, X3>), grid, dim3(256), smem_bytes, st, (const T*)qkv, (T*)out, lse, B, N, sc.c2,
+    ensure_dynamic_lds(once, &attn_fwd_kernel<T, X3, LENS>, smem_bytes);
+    hipLaunchKernelGGL((attn_fwd_kernel<T, X3, LENS>), grid, dim3(256), smem_bytes, st, (const T*)qkv, (T*)out, lse, B, N, sc.c2,
                        q_rows, out_a3 ? 1 : 0);
     return check_launch("maest_attn_fwd");
 }
@@ -2229,6 +2287,7 @@ extern "C" int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B
     MAEST_REQUIRE(q_rows > 0 && q_rows <= N, "maest_attn_fwd_rows: q_rows = %d outside 1..N", q_rows);
     if (dtype & (MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN)) {     // the attention maps: `out` is fp32 [B, 12, q_rows, N] / [B, q_rows, N]
         const int base = dtype & ~(MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN);
+        MAEST_REQUIRE(!(dtype & MAEST_ATTN_LENS), "maest_attn_fwd: MAEST_ATTN_LENS with MAEST_ATTN_PROBS (dtype %d): the maps know no token counts", dtype);
         MAEST_REQUIRE(dtype & MAEST_ATTN_PROBS, "maest_attn_fwd: MAEST_ATTN_PROBS_MEAN without MAEST_ATTN_PROBS (dtype %d)", dtype);
         MAEST_REQUIRE(base != MAEST_F32X3_A3, "maest_attn_fwd: MAEST_ATTN_PROBS writes fp32 probabilities: no MAEST_F32X3_A3 form");
         MAEST_REQUIRE(base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS,
@@ -2240,6 +2299,19 @@ extern "C" int maest_attn_fwd_rows(const void* qkv, void* out, float* lse, int B
         if (base == MAEST_F32X3) return attn_probs_launch<float, true>(qkv, out, B, N, scp, q_rows, mean, (hipStream_t)stream);
         return base == MAEST_F32 ? attn_probs_launch<float>(qkv, out, B, N, scp, q_rows, mean, (hipStream_t)stream)
                                  : attn_probs_launch<bf16_t>(qkv, out, B, N, scp, q_rows, mean, (hipStream_t)stream);
+    }
+    if (dtype & MAEST_ATTN_LENS) {     // token counts per clip: `lse` carries const int32_t* n_tok [B], nothing is saved
+        const int base = dtype & ~MAEST_ATTN_LENS;
+        MAEST_REQUIRE(base == MAEST_F32 || base == MAEST_BF16 || base == MAEST_F32X3 || base == MAEST_BF16_QS || base == MAEST_F32X3_A3,
+                      "maest_attn_fwd: bad dtype %d under MAEST_ATTN_LENS", base);
+        MAEST_REQUIRE(lse != nullptr, "maest_attn_fwd: MAEST_ATTN_LENS reads the token counts (int32 [B]) from `lse`: null pointer");
+        MAEST_REQUIRE(((uintptr_t)lse % 4) == 0, "maest_attn_fwd: MAEST_ATTN_LENS: the token counts want 4-byte alignment");
+        MAEST_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)out % 16) == 0, "maest_attn_fwd: 16-byte alignment");
+        const AttnScale scl = attn_scale(scale, base == MAEST_BF16_QS);
+        if (base == MAEST_F32X3 || base == MAEST_F32X3_A3)
+            return attn_fwd_launch<float, true, true>(qkv, out, lse, B, N, scl, false, q_rows, (hipStream_t)stream, base == MAEST_F32X3_A3);
+        return base == MAEST_F32 ? attn_fwd_launch<float, false, true>(qkv, out, lse, B, N, scl, false, q_rows, (hipStream_t)stream)
+                                 : attn_fwd_launch<bf16_t, false, true>(qkv, out, lse, B, N, scl, base == MAEST_BF16_QS, q_rows, (hipStream_t)stream);
     }
     MAEST_REQUIRE(dtype == MAEST_F32 || dtype == MAEST_BF16 || dtype == MAEST_F32X3 || dtype == MAEST_BF16_QS || dtype == MAEST_F32X3_A3,
                   "maest_attn_fwd: bad dtype %d", dtype);
@@ -2260,6 +2332,7 @@ extern "C" int maest_attn_fwd(const void* qkv, void* out, float* lse, int B, int
 extern "C" int maest_attn_bwd_rows(const void* qkv, const void* out, const void* dout, const float* lse,
                                    float* delta, void* dqkv, int B, int N, int dtype, float scale, int q_rows,
                                    void* stream) {
+    // (MAEST_ATTN_LENS is a form of maest_attn_fwd(_rows) alone: here it is a bit no dtype code has -- "bad dtype" below, with and without MAEST_ATTN_APPLY)
     // MAEST_ATTN_APPLY_HEADS is a form of MAEST_ATTN_APPLY alone: not of the backward, and the attention maps belong to maest_attn_fwd_rows
     MAEST_REQUIRE(!(dtype & MAEST_ATTN_APPLY_HEADS) || !(dtype & (MAEST_ATTN_PROBS | MAEST_ATTN_PROBS_MEAN)),
                   "maest_attn_bwd: MAEST_ATTN_APPLY_HEADS with MAEST_ATTN_PROBS (dtype %d): the per-head form belongs to MAEST_ATTN_APPLY", dtype);

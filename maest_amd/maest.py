@@ -409,8 +409,10 @@ class _Engine:
 
     def _forward(self, x3: torch.Tensor, dt, *, toffset: int, tok_ft: torch.Tensor, perm, lam, stripes=None,
                  stop_block: int = -1, return_self_attention: bool = False, save: bool = False, x3m=None, f16: bool = False, tap=None,
-                 explain: bool = False, tap_x=None, full_last: bool = False):
+                 explain: bool = False, tap_x=None, full_last: bool = False, n_tok=None):
         """x3: fp32 [B, F, T] on the device; tok_ft: int32 [P, 2] kept patch tokens.  Returns (outputs, ctx).
+        n_tok (ragged batches; only with a table per clip): int32 [B] on the device, clip b's real rows 2 + its kept tokens, the rest of
+        its table MAEST_TOK_BLANK pads at the end -- handed to every block's attention (MAEST_ATTN_LENS), nothing else changes.
         x3m: split-bf16 products on the fp32 tensors (the model's resolved mode; None: model.precision == "bf16x3").
         tap (maest_amd/explain.py: the attention maps and the rollout): called as tap(i, qkv, (B, N, scale, x3m, qs)) right behind block
         i's qkv GEMM, with what an attention kernel needs to read that tensor; None: exactly the launches below.
@@ -434,6 +436,11 @@ class _Engine:
                                  "intermediate-block outputs (save, tap, tap_x, stop_block)")
             if tuple(tok_ft.shape[::2]) != (B, 2):
                 raise ValueError(f"tok_ft of shape {tuple(tok_ft.shape)} for a batch of {B} clips: [B, P, 2] wanted")
+        if n_tok is not None:
+            if not clip_tokens:
+                raise ValueError("token counts per clip (n_tok) go with a table of kept tokens per clip: tok_ft [B, P, 2]")
+            if n_tok.dtype != torch.int32 or tuple(n_tok.shape) != (B,) or n_tok.device != x3.device:
+                raise ValueError(f"n_tok must be an int32 tensor [{B}] on {x3.device}, got {n_tok.dtype} {tuple(n_tok.shape)} on {n_tok.device}")
         P = int(tok_ft.shape[-2])
         N = 2 + P
         M = B * N
@@ -545,7 +552,7 @@ class _Engine:
             # and only the per-token part of the block is restricted)
             q_rows = HEAD_TOKENS if tail and (not save or ops.attn_bwd_rows_supported(dt, N)) else None
             fast_blk = fast3 and not tail and not (i == stop_block and return_self_attention)
-            r = ops.attn_fwd(qkv, B, N, scale, save_lse=save, q_rows=q_rows, x3=x3m, q_prescaled=qs, out_split3=fast_blk)
+            r = ops.attn_fwd(qkv, B, N, scale, save_lse=save, q_rows=q_rows, x3=x3m, q_prescaled=qs, out_split3=fast_blk, n_tok=n_tok)
             ao, lse = r if save else (r, None)
             ao_full, x_full, Mb = ao, x, M
             if tail:      # from here on the block lives on [B * 2, 768]
@@ -1434,6 +1441,9 @@ class MAEST(nn.Module):
         kwa = kwb = kw
         if tok.dim() == 3:
             kwa, kwb = dict(kw, tok_ft=tok[:h]), dict(kw, tok_ft=tok[h:])
+        n_tok = kw.get("n_tok")
+        if n_tok is not None:                  # (ragged batches: each half its own clips' counts)
+            kwa["n_tok"], kwb["n_tok"] = n_tok[:h], n_tok[h:]
         built = wc.builds
         outs_a, _ = eng.forward(xa, dt, **kwa)
         if wc.builds != built:
@@ -1445,6 +1455,8 @@ class MAEST(nn.Module):
         xb.record_stream(side)                 # (allocated on the caller's stream, read on the other one)
         if tok.dim() == 3:
             tok.record_stream(side)
+        if n_tok is not None:
+            n_tok.record_stream(side)
         cur.wait_stream(side)
         for o in outs_b:
             if o is not None:
@@ -1660,7 +1672,7 @@ class MAEST(nn.Module):
         return explain.attention_heads(self, x, target, start, blocks, alpha, melspectrogram_input, target_dist=target_dist,
                                        grad_scale=grad_scale, _patchout=_patchout)
 
-    def forward_tokens(self, x, keep, blank=None, melspectrogram_input: bool = False, *, _patchout=None):
+    def forward_tokens(self, x, keep, blank=None, melspectrogram_input: bool = False, *, _patchout=None, **options):
         """``forward`` on a chosen set of patch tokens PER CLIP: what ``self(x)`` returns, from one evaluation forward under no_grad (eager, the
         two-stream split included; no HIP-graph replay, and nothing is recorded).
 
@@ -1671,11 +1683,33 @@ class MAEST(nn.Module):
         shorter.  Tokens where blank[b] is set stay in the sequence with zeroed content: the convolution's bias plus the positional terms.
         Every row of keep must hold the same count, at least 1, and blank must be a subset of keep (ValueError; TypeError for masks that
         are no bool tensors; the value checks cost one device sync).  Gradients, maps, pools and HIP-graph replay on per-clip tokens are
-        not offered."""
-        return perturb.forward_tokens(self, x, keep, blank, melspectrogram_input, _patchout=_patchout)
+        not offered.
+
+        options: one keyword, ``ragged=False`` (any other: TypeError, as for an unknown keyword; it is taken through ``**options`` because
+        the keyword-only list of this method is pinned as it was before ragged batches).
+        ragged=True (a bool: TypeError otherwise): the rows of keep may hold DIFFERENT counts, each at least 1.  The batch runs at the
+        longest clip's length: every clip's kept tokens in ascending sequence order, then blank pad slots, and every block's attention
+        is told the clip's own token count (MAEST_ATTN_LENS: pads are neither attended nor computed there).  Cost: the per-token
+        kernels run B x max count rows, attention runs the sum of the squared counts; sorting or bucketing clips by length is the
+        caller's choice.  With equal counts the call is the ragged=False one, bit for bit."""
+        opt = perturb.take_options("forward_tokens", options, ragged=False)
+        return perturb.forward_tokens(self, x, keep, blank, melspectrogram_input, _patchout=_patchout, ragged=opt["ragged"])
+
+    def forward_lengths(self, x, frames):
+        """Clips of different durations in one batch: what ``self(x, melspectrogram_input=True)`` returns, from one evaluation forward under
+        no_grad (eager; ValueError in train() mode), with clip b run on its first frames[b] mel frames only.
+
+        x: a mel batch [B, F, T] or [B, 1, F, T], padded to the longest clip (1-D / 2-D audio: ValueError -- the STFT's edge padding makes
+        a padded waveform differ from the clip alone).  frames: an integer tensor or a sequence of ints [B], 16 <= frames[b] <= T
+        (TypeError / ValueError, before any launch).  Clip b runs on the tokens (f, t) of the call's evaluation token sequence with
+        t < Tp_b = (frames[b] - 16) // stride_t + 1: the time patches that lie wholly inside it.  Frames >= frames[b] of x are never read
+        and may hold anything, NaN included.  For a model without evaluation-time time-patchout (the default) clip b equals
+        ``model(x[b:b+1, ..., :frames[b]], melspectrogram_input=True)``.  The batch runs as ``forward_tokens(ragged=True)`` does, at that
+        cost: per-token kernels on B x the longest clip's rows, attention on the sum of the squared token counts."""
+        return perturb.forward_lengths(self, x, frames)
 
     def perturbation_curve(self, x, scores, target, order: str = "positive", fractions=None, mode: str = "drop", row: int = 0,
-                           melspectrogram_input: bool = False, *, seed: int = 0, _patchout=None) -> "PerturbationCurve":
+                           melspectrogram_input: bool = False, *, seed: int = 0, _patchout=None, **options) -> "PerturbationCurve":
         """The perturbation test of Chefer, Gur & Wolf 2021 (deletion curves, MoRF / LeRF) for a score per patch token: remove a growing
         fraction of each clip's tokens in the order of its scores and record the target label's probability.  Faithful scores make it
         fall fast under order="positive" (the highest scores leave first) and slowly under "negative"; scores="random" is the baseline.
@@ -1689,9 +1723,16 @@ class MAEST(nn.Module):
         token-level counterpart of zeroing pixels, without the leak the overlap of the 16 x 16 patches at stride 10 would cause.
         target: a label index, or an integer tensor [B] with one per clip.  Each step is one ``forward_tokens``.  Returns
         PerturbationCurve: fractions, removed [S], logits [S, B, C], logits_dist, logit and prob [S, B], auc [B], order, mode, tokens,
-        keep_mask(step)."""
+        keep_mask(step).
+
+        options: one keyword, ``by="fraction"`` (any other: TypeError; taken through ``**options`` for the reason given in ``forward_tokens``).
+        by="mass" (the sufficiency / comprehensiveness form; needs order="positive" and scores >= 0 with a positive sum in every clip,
+        ValueError otherwise): at fraction phi clip b removes the smallest r whose r highest scores sum to >= phi x the clip's total
+        (float64 cumulative sums in the removal order; phi = 0 removes nothing; r is capped at P - 1) -- a different count per clip, so
+        ``removed`` is int64 [S, B] and mode="drop" runs through the ragged forward (``forward_tokens(ragged=True)``)."""
+        opt = perturb.take_options("perturbation_curve", options, by="fraction")
         return perturb.perturbation_curve(self, x, scores, target, order, fractions, mode, row, melspectrogram_input, seed=seed,
-                                          _patchout=_patchout)
+                                          _patchout=_patchout, by=opt["by"])
 
 
 # --------------------------------------------------------------------------------------

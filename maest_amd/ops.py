@@ -380,11 +380,26 @@ def _attn_flops(B, N, q_rows, per_pair):
     return per_pair * B * HEADS * nq * N * HEAD_DIM
 
 
+def _attn_flops_lens(n_tok, N, q_rows, per_pair):
+    """_attn_flops under token counts: sum over the clips of (real queries of the written tiles) x n_b keys.  Read from the device only
+    while a KernelTimer records this call (one sync)."""
+    if _TIMER is None or (_TIMER.kinds is not None and "maest_attn_fwd" not in _TIMER.kinds):
+        return 0.0
+    n = n_tok.to(torch.int64)
+    nq = n if q_rows is None or q_rows >= N else torch.clamp(n, max=min(N, -(-q_rows // 32) * 32))
+    return per_pair * HEADS * int((nq * n).sum()) * HEAD_DIM
+
+
 def attn_fwd(qkv: torch.Tensor, B: int, N: int, scale: float, save_lse=False, q_rows=None, x3: bool = False, q_prescaled=False,
-             out_split3=False):
+             out_split3=False, n_tok=None):
     """q_rows: only the first q_rows queries of every clip are wanted (rows beyond the 32-row tile that holds them are
-    left unwritten in `out` / `lse`).  q_prescaled (bf16 only): the q columns hold scale * log2(e) * q (MAEST_BF16_QS)."""
-    _chk(qkv)
+    left unwritten in `out` / `lse`).  q_prescaled (bf16 only): the q columns hold scale * log2(e) * q (MAEST_BF16_QS).
+    n_tok (MAEST_ATTN_LENS): int32 [B] on the device, clip b attends over its first n_tok[b] rows (1 .. N, the caller's to check) and the
+    written rows behind them leave as zeros; an evaluation form: no save_lse."""
+    _chk(qkv, n_tok)
+    if n_tok is not None:
+        assert not save_lse, "n_tok (MAEST_ATTN_LENS) saves no lse"
+        assert n_tok.dtype == torch.int32 and tuple(n_tok.shape) == (B,) and n_tok.device == qkv.device
     assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
     assert qkv.shape == (B * N, 3 * EMBED)
     # out_split3 (x3 mode): the fp32 result leaves as MAEST_SPLIT3_A rows, bf16 [B * N, 3 * 768] -- the A operand of the proj GEMM
@@ -392,8 +407,12 @@ def attn_fwd(qkv: torch.Tensor, B: int, N: int, scale: float, save_lse=False, q_
     out = (torch.empty((B * N, 3 * EMBED), dtype=torch.bfloat16, device=qkv.device) if out_split3
            else torch.empty((B * N, EMBED), dtype=qkv.dtype, device=qkv.device))
     lse = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device) if save_lse else None
-    _timed_call("maest_attn_fwd", _attn_flops(B, N, q_rows, 4.0), _p(qkv), _p(out), _p(lse), B, N,
-                F32X3_A3 if out_split3 else (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)), scale,
+    code = F32X3_A3 if out_split3 else (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3))
+    if n_tok is not None:
+        _timed_call("maest_attn_fwd", _attn_flops_lens(n_tok, N, q_rows, 4.0), _p(qkv), _p(out), _p(n_tok), B, N, code | _lib.ATTN_LENS, scale,
+                    N if q_rows is None else q_rows, _s(qkv), _entry="maest_attn_fwd_rows")
+        return out
+    _timed_call("maest_attn_fwd", _attn_flops(B, N, q_rows, 4.0), _p(qkv), _p(out), _p(lse), B, N, code, scale,
                 N if q_rows is None else q_rows, _s(qkv), _entry="maest_attn_fwd_rows")
     return (out, lse) if save_lse else out
 

@@ -13,6 +13,8 @@ from .explain import _INT_DTYPES, AttentionRelevance, AttentionRollout
 
 ORDERS = ("positive", "negative")
 MODES = ("drop", "blank")
+BYS = ("fraction", "mass")
+PATCH = 16      # frames (and bands) of a patch: the convolution's kernel (models/maest.py:214-241)
 DEFAULT_FRACTIONS = tuple(k / 10 for k in range(10))
 
 
@@ -36,6 +38,35 @@ def keep_mask(rank: torch.Tensor, removed: int) -> torch.Tensor:
     return keep
 
 
+def keep_mask_counts(rank: torch.Tensor, removed: torch.Tensor) -> torch.Tensor:
+    """keep_mask with a count per clip: removed int64 [B], 0 .. P each -> bool [B, P], False at the first removed[b] tokens of clip b's order."""
+    B, P = rank.shape
+    removed = removed.to(rank.device)
+    if tuple(removed.shape) != (B,) or not bool(((removed >= 0) & (removed <= P)).all()):
+        raise ValueError(f"removed must hold {B} counts in 0 .. {P}")
+    gone = torch.arange(P, device=rank.device).unsqueeze(0) < removed.unsqueeze(1)      # in removal order
+    return torch.ones((B, P), dtype=torch.bool, device=rank.device).scatter_(1, rank, ~gone)
+
+
+def mass_removed_counts(scores: torch.Tensor, rank: torch.Tensor, fractions) -> torch.Tensor:
+    """by="mass": scores [B, P] >= 0 with a positive sum per clip, rank = removal_order(scores, "positive") -> int64 [S, B]: at fraction
+    phi clip b removes the smallest r whose r highest scores sum to >= phi x the clip's total (float64 cumulative sums in the order of
+    `rank`; the total is the last of them), capped at P - 1.  phi = 0 removes nothing."""
+    P = scores.shape[1]
+    cum = scores.gather(1, rank).to(torch.float64).cumsum(1)                             # c_1 .. c_P; c_0 = 0
+    cum = torch.cat([torch.zeros_like(cum[:, :1]), cum], 1)
+    out = []
+    for f in fractions:
+        r = (cum < float(f) * cum[:, -1:]).sum(1)                                        # c_j ascends: the first j with c_j >= phi c_P
+        out.append(r.clamp(max=P - 1))
+    return torch.stack(out).to(torch.int64)
+
+
+def frames_to_time_patches(frames: torch.Tensor, stride_t: int) -> torch.Tensor:
+    """frames int [B] >= 16 -> the time patches that lie wholly inside each clip, Tp_b = (frames[b] - 16) // stride_t + 1."""
+    return torch.div(frames.to(torch.int64) - PATCH, int(stride_t), rounding_mode="floor") + 1
+
+
 def random_scores(B: int, P: int, seed: int) -> torch.Tensor:
     """The "random" ranking: per clip a permutation of 0 .. P - 1 as fp32 scores, drawn from a CPU torch.Generator seeded with `seed`."""
     gen = torch.Generator(device="cpu").manual_seed(int(seed))
@@ -57,7 +88,7 @@ def trapezoid_auc(prob: torch.Tensor, fractions) -> torch.Tensor:
 
 class PerturbationCurve:
     """What MAEST.perturbation_curve returns.  fractions: the S fractions as floats; removed: int64 [S] on the CPU, r_k = floor(fraction_k * P)
-    tokens removed per clip at step k.  logits: fp32 [S, B, C], detached (logits_dist: the distillation head's, with
+    tokens removed per clip at step k (by="mass": int64 [S, B] on the CPU, a count per step and clip).  logits: fp32 [S, B, C], detached (logits_dist: the distillation head's, with
     distilled_type="separated"; else None); logit, prob: [S, B], the target label's logit and its sigmoid; auc: [B], the trapezoid of prob
     over the fractions divided by their span (None for a single step) -- small after a "positive" run and large after a "negative" one
     when the scores are faithful.  order, mode: as given; tokens: int32 [P, 2], (frequency patch, time patch) of the call's token sequence;
@@ -70,12 +101,29 @@ class PerturbationCurve:
 
     def keep_mask(self, step: int) -> torch.Tensor:
         """bool [B, P]: the tokens step `step` left in place with their content (mode "blank": the others stayed, with zeroed content)."""
-        return keep_mask(self._rank, int(self.removed[step]))
+        r = self.removed[step]
+        return keep_mask_counts(self._rank, r) if r.dim() == 1 else keep_mask(self._rank, int(r))
 
 
 # ------------------------------------------------------------------------------------------------ argument checks (before any launch of the model)
-def _check_masks(keep, blank) -> int:
-    """The form and the values of the masks of forward_tokens -> the number of tokens every clip keeps (masks on a device: one sync)."""
+def take_options(method: str, given: dict, **defaults) -> dict:
+    """The keywords a method takes through ``**options`` (MAEST.forward_tokens: ragged; MAEST.perturbation_curve: by) -> their values,
+    defaults filled in; any other keyword is the TypeError Python raises for an unknown one."""
+    for name in given:
+        if name not in defaults:
+            raise TypeError(f"{method}() got an unexpected keyword argument {name!r}")
+    return dict(defaults, **given)
+
+
+def _check_ragged(ragged):
+    if not isinstance(ragged, bool):
+        raise TypeError(f"ragged must be a bool, got {ragged!r}")
+
+
+def _check_masks(keep, blank, ragged: bool = False):
+    """The form and the values of the masks of forward_tokens -> the number of tokens every clip keeps (masks on a device: one sync).
+    ragged: the rows of keep may hold different counts, each >= 1 -> (the largest count, the counts int64 [B] on keep's device -- None
+    when they are all equal: such a call is the plain one)."""
     for name, m in (("keep", keep), ("blank", blank)):
         if m is None and name == "blank":
             continue
@@ -92,13 +140,34 @@ def _check_masks(keep, blank) -> int:
     counts = keep.sum(1)
     stray = (blank.to(keep.device) & ~keep).any() if blank is not None else torch.zeros((), dtype=torch.bool, device=keep.device)
     lo, hi, stray = (int(v) for v in torch.stack([counts.min(), counts.max(), stray.to(counts.dtype)]).cpu())
-    if lo != hi:
+    if lo != hi and not ragged:
         raise ValueError(f"every clip must keep the same number of tokens: the rows of keep hold {lo} .. {hi}")
     if lo < 1:
-        raise ValueError("keep removes every patch token")
+        raise ValueError("keep removes every patch token" if not ragged else "keep removes every patch token of a clip: a row of keep holds no token")
     if stray:
         raise ValueError("blank must be a subset of keep")
-    return lo
+    return (hi, counts if lo != hi else None) if ragged else lo
+
+
+def _check_frames(frames, B: int, T: int) -> torch.Tensor:
+    """frames of forward_lengths -> int64 [B] on the CPU."""
+    if torch.is_tensor(frames):
+        if frames.dtype not in _INT_DTYPES:
+            raise TypeError(f"frames must be an integer tensor or a sequence of ints [B], got a {frames.dtype} tensor")
+        fr = frames.detach().cpu().to(torch.int64)
+    else:
+        if isinstance(frames, (str, bytes)) or not hasattr(frames, "__iter__"):
+            raise TypeError(f"frames must be an integer tensor or a sequence of ints [B], got {frames!r}")
+        vals = list(frames)
+        for v in vals:
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"frames must be an integer tensor or a sequence of ints [B], got an element {v!r}")
+        fr = torch.tensor(vals, dtype=torch.int64)
+    if tuple(fr.shape) != (B,):
+        raise ValueError(f"frames has shape {tuple(fr.shape)}: this call has B = {B} clips, [B] wanted")
+    if int(fr.min()) < PATCH or int(fr.max()) > T:
+        raise ValueError(f"frames must lie in {PATCH} .. {T} (one patch .. the padded length), got {int(fr.min())} .. {int(fr.max())}")
+    return fr
 
 
 def _check_fractions(fractions):
@@ -162,46 +231,101 @@ def _check_scores(scores, row):
 
 
 # ------------------------------------------------------------------------------------------------ the forward
-def _clip_table(tok: torch.Tensor, keep: torch.Tensor, blank, K: int) -> torch.Tensor:
+def _clip_table(tok: torch.Tensor, keep: torch.Tensor, blank, K: int, counts=None) -> torch.Tensor:
     """tok int32 [P, 2], keep / blank bool [B, P] with K kept tokens in every row -> int32 [B, K, 2]: per clip its kept tokens in
-    ascending sequence order, the blank ones with TOK_BLANK in the f word."""
+    ascending sequence order, the blank ones with TOK_BLANK in the f word.  counts (ragged batches; int [B], K their largest): clip b
+    keeps counts[b] tokens, and the K - counts[b] slots behind them are pads: TOK_BLANK entries (of removed tokens, whose content is
+    never read) that the attention does not see (MAEST_ATTN_LENS)."""
     idx = torch.sort((~keep).to(torch.int8), dim=1, stable=True).indices[:, :K]      # kept positions first, each group ascending
     table = tok[idx]
     if blank is not None:
         table[..., 0] |= blank.gather(1, idx).to(torch.int32) * TOK_BLANK
+    if counts is not None:
+        pad = torch.arange(K, device=idx.device).unsqueeze(0) >= counts.to(idx.device).unsqueeze(1)
+        table[..., 0] |= pad.to(torch.int32) * TOK_BLANK
     return table.contiguous()
 
 
-def _forward_resolved(model, x3, dt, kw, keep, blank, K):
+def _forward_resolved(model, x3, dt, kw, keep, blank, K, counts=None):
     """One evaluation forward of a resolved call (MAEST._resolve_call) on per-clip tokens: masks that passed _check_masks (or that the
-    curve made itself), K kept tokens in every row."""
+    curve made itself), K kept tokens in every row -- or, counts (int [B], not all equal), counts[b] <= K of them in row b: the ragged
+    forward, n_tok = 2 + counts."""
     tok = kw["tok_ft"]
     B, P = int(x3.shape[0]), int(tok.shape[0])
     if tuple(keep.shape) != (B, P):
         raise ValueError(f"keep has shape {tuple(keep.shape)}: this call has B = {B} clips of P = {P} patch tokens")
     keep = keep.to(tok.device)
     blank = None if blank is None else blank.to(tok.device)
+    kw = dict(kw, tok_ft=_clip_table(tok, keep, blank, K, counts))
+    if counts is not None:
+        kw["n_tok"] = (counts.to(tok.device) + 2).to(torch.int32).contiguous()
     with torch.no_grad():
-        return model._eval_forward(x3, dt, dict(kw, tok_ft=_clip_table(tok, keep, blank, K)))
+        return model._eval_forward(x3, dt, kw)
 
 
-def forward_tokens(model, x, keep, blank, melspectrogram_input, *, _patchout):
-    K = _check_masks(keep, blank)
+def forward_tokens(model, x, keep, blank, melspectrogram_input, *, _patchout, ragged=False):
+    _check_ragged(ragged)
+    K, counts = _check_masks(keep, blank, True) if ragged else (_check_masks(keep, blank), None)
     x3, dt, kw, _, _ = model._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
-    return _forward_resolved(model, x3, dt, kw, keep, blank, K)
+    return _forward_resolved(model, x3, dt, kw, keep, blank, K, counts)
 
 
-def perturbation_curve(model, x, scores, target, order, fractions, mode, row, melspectrogram_input, *, seed, _patchout):
+def forward_lengths(model, x, frames):
+    if not torch.is_tensor(x):
+        raise TypeError(f"x must be a mel batch [B, F, T] or [B, 1, F, T], got {type(x).__name__}")
+    if x.dim() in (1, 2):
+        raise ValueError("forward_lengths takes mel batches [B, F, T] / [B, 1, F, T] only: the STFT's edge padding makes a padded waveform "
+                         "differ from the clip alone (waveform input is not offered)")
+    if x.dim() not in (3, 4):
+        raise ValueError(f"x must be a mel batch [B, F, T] or [B, 1, F, T], got shape {tuple(x.shape)}")
+    if model.training:
+        raise ValueError("forward_lengths is an evaluation forward: call model.eval() first (training and gradients on ragged batches are "
+                         "not offered)")
+    fr = _check_frames(frames, int(x.shape[0]), int(x.shape[-1]))
+    x3, dt, kw, _, _ = model._resolve_call(x, True, None, None, None, recording=False)
+    tok = kw["tok_ft"]
+    tp = frames_to_time_patches(fr, model.patch_embed.stride[1]).to(tok.device)
+    keep = tok[:, 1].to(torch.int64).unsqueeze(0) < tp.unsqueeze(1)
+    K, counts = _check_masks(keep, None, True)
+    return _forward_resolved(model, x3, dt, kw, keep, None, K, counts)
+
+
+def _fraction_steps(model, x3, dt, kw, rank, removed, mode, P):
+    steps = []
+    for r in removed:
+        m = keep_mask(rank, r)
+        if mode == "drop":
+            steps.append(_forward_resolved(model, x3, dt, kw, m, None, K=P - r))
+        else:
+            steps.append(_forward_resolved(model, x3, dt, kw, torch.ones_like(m), ~m, K=P))
+    return steps
+
+
+def _check_mass_scores(scores):
+    """by="mass": every score >= 0 and a positive sum in every clip."""
+    if bool((scores < 0).any()):
+        raise ValueError("by='mass' needs scores >= 0 (the mass of a clip is the sum of its scores)")
+    if not bool((scores.to(torch.float64).sum(1) > 0).all()):
+        raise ValueError("by='mass' needs a positive sum of scores in every clip")
+
+
+def perturbation_curve(model, x, scores, target, order, fractions, mode, row, melspectrogram_input, *, seed, _patchout, by="fraction"):
     if order not in ORDERS:
         raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    if not isinstance(by, str) or by not in BYS:
+        raise ValueError(f"by must be one of {BYS}, got {by!r}")
+    if by == "mass" and order != "positive":
+        raise ValueError(f"by='mass' removes the highest scores first: order must be 'positive', got {order!r}")
     fractions = _check_fractions(fractions)
     if isinstance(seed, bool) or not isinstance(seed, int):
         raise TypeError(f"seed must be an int, got {seed!r}")
     C = model.head[1].out_features
     _check_curve_target(target, C)
     scores, score_tokens = _check_scores(scores, row)
+    if by == "mass" and scores is not None:
+        _check_mass_scores(scores)
     x3, dt, kw, _, _ = model._resolve_call(x, melspectrogram_input, None, _patchout, None, recording=False)
     tok = kw["tok_ft"]
     dev = tok.device
@@ -215,19 +339,28 @@ def perturbation_curve(model, x, scores, target, order, fractions, mode, row, me
     if score_tokens is not None and not torch.equal(score_tokens.to(dev), tok):
         raise ValueError("the scores were computed on another token sequence than this call's (compare .tokens: patchout draws differ)")
     rank = removal_order(scores.to(dev), order)
-    removed = removed_counts(fractions, P)
-    steps = []
-    for r in removed:
-        m = keep_mask(rank, r)
-        if mode == "drop":
-            steps.append(_forward_resolved(model, x3, dt, kw, m, None, K=P - r))
-        else:
-            steps.append(_forward_resolved(model, x3, dt, kw, torch.ones_like(m), ~m, K=P))
+    if by == "mass":
+        _check_mass_scores(scores)      # (the "random" permutation of a single token sums to 0)
+        removed = mass_removed_counts(scores.to(dev), rank, fractions)
+        steps = []
+        for r in removed:
+            m = keep_mask_counts(rank, r)
+            if mode == "drop":
+                kept = P - r
+                lo, hi = int(kept.min()), int(kept.max())
+                steps.append(_forward_resolved(model, x3, dt, kw, m, None, K=hi, counts=kept if lo != hi else None))
+            else:
+                steps.append(_forward_resolved(model, x3, dt, kw, torch.ones_like(m), ~m, K=P))
+        removed = removed.cpu()
+    else:
+        removed = removed_counts(fractions, P)
+        steps = _fraction_steps(model, x3, dt, kw, rank, removed, mode, P)
+        removed = torch.tensor(removed, dtype=torch.int64)
     logits = torch.stack([o[0] for o in steps])
     logits_dist = torch.stack([o[1] for o in steps]) if len(steps[0]) == 3 else None
     tgt = (torch.full((B,), target, dtype=torch.long) if isinstance(target, int) else target.detach().long()).to(dev)
     logit = logits.gather(2, tgt.reshape(1, B, 1).expand(len(steps), B, 1)).squeeze(2)
     prob = torch.sigmoid(logit)
     auc = trapezoid_auc(prob, fractions) if len(steps) > 1 else None
-    return PerturbationCurve(fractions, torch.tensor(removed, dtype=torch.int64), logits, logit, prob, auc, order, mode, tok, tgt, rank,
+    return PerturbationCurve(fractions, removed, logits, logit, prob, auc, order, mode, tok, tgt, rank,
                              logits_dist=logits_dist)
