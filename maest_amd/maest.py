@@ -146,7 +146,6 @@ class _Weights:
 
     def get(self, p: torch.Tensor, dtype, transposed=False, pad_cols_to: int = 0):
         key = self._key(p, dtype, transposed, pad_cols_to)
-        ver = p._version
         hit = self._fresh(key, p)
         if hit is not None:
             return hit
@@ -167,7 +166,7 @@ class _Weights:
                 out = ops.transpose(lp, ops.round_up(w2.shape[0], pad_cols_to))
             else:
                 _, out = ops.cast_weights(w2, dtype, want=False, want_t=True)
-        self._cache[key] = (ver, out, weakref.ref(p))
+        self._store(key, p, out)
         return out
 
     def _fresh(self, key, p):
@@ -178,56 +177,56 @@ class _Weights:
             return hit[1]
         return None
 
+    def _store(self, key, p, out):
+        self._cache[key] = (p._version, out, weakref.ref(p))
+
+    def _build(self, params, key, dtype, *, want=True, want_t=False, rows=None, src=lambda p: p.detach(), view=lambda o: o):
+        """The one way copies made by ops.cast_weights_multi enter the cache.  key(p, transposed) names a copy of parameter p; the
+        parameters one of whose wanted copies is not fresh are rebuilt together, in ONE launch (`src`: the fp32 matrix handed to it,
+        `rows`: the row-scaled rows of p's plain copy, `view`: the shape a copy is cached in).  Returns the plain copies in order."""
+        stale = [p for p in params if any(self._fresh(key(p, tr), p) is None for tr in ((False, True) if want_t else (False,)))]
+        if stale:
+            self.builds += 1
+            scaled = {} if rows is None else dict(scaled_rows=[rows(p) for p in stale], row_scale=self.row_scale)
+            outs = ops.cast_weights_multi([src(p) for p in stale], dtype, want=want, want_t=want_t, **scaled)
+            for p, copies in zip(stale, outs):
+                for tr, o in zip((False, True), copies):
+                    if o is not None:
+                        self._store(key(p, tr), p, view(o))
+        return [self._cache[key(p, False)][1] for p in params] if want else None
+
     def refresh(self, params, dtype, with_t: bool):
         """Bring the plain (and, for training, transposed) operand copies of `params` up to date in one launch."""
         if dtype == torch.float32 and not with_t:
             return
-        stale = []
-        for p in params:
-            for tr in ((False, True) if with_t else (False,)):
-                if self._fresh(self._key(p, dtype, tr), p) is None:
-                    stale.append(p)
-                    break
-        if not stale:
-            return
-        self.builds += 1
-        outs = ops.cast_weights_multi([p.detach() for p in stale], dtype, want=dtype != torch.float32, want_t=with_t,
-                                      scaled_rows=[self._srows(p, dtype) for p in stale], row_scale=self.row_scale)
-        for p, (o, ot) in zip(stale, outs):
-            if o is not None:
-                self._cache[self._key(p, dtype, False)] = (p._version, o, weakref.ref(p))
-            if ot is not None:
-                self._cache[self._key(p, dtype, True)] = (p._version, ot, weakref.ref(p))
+        self._build(params, lambda p, tr: self._key(p, dtype, tr), dtype, want=dtype != torch.float32, want_t=with_t,
+                    rows=lambda p: self._srows(p, dtype))
 
     def split3(self, params):
         """MAEST_SPLIT3_B copies (bf16 [out, 3 * in]: hi | lo | hi) of fp32 weight matrices, stale ones rebuilt in one launch; cached
         like the other operand copies.  Returns them in order."""
-        key = lambda p: (id(p), "split3b", False, 0)
-        stale = [p for p in params if self._fresh(key(p), p) is None]
-        if stale:
-            self.builds += 1
-            outs = ops.cast_weights_multi([p.detach() for p in stale], ops.SPLIT3, want=True, want_t=False)
-            for p, (o, _) in zip(stale, outs):
-                self._cache[key(p)] = (p._version, o, weakref.ref(p))
-        return [self._cache[key(p)][1] for p in params]
+        return self._build(params, lambda p, tr: (id(p), "split3b", False, 0), ops.SPLIT3)
 
     def scaled_biases(self, biases, rows: int):
         """fp32 copies of `biases` with the first `rows` entries multiplied by row_scale (the q part of the qkv biases beside the
         row-scaled weight copies), all in one launch; cached like the weight copies."""
-        bkey = lambda b: (id(b), "scaled-bias", False, rows, self.row_scale)
-        stale = [b for b in biases if self._fresh(bkey(b), b) is None]
-        if stale:
-            self.builds += 1
-            outs = ops.cast_weights_multi([b.detach().reshape(-1, 1) for b in stale], torch.float32, want=True, want_t=False,
-                                          scaled_rows=[rows] * len(stale), row_scale=self.row_scale)
-            for b, (o, _) in zip(stale, outs):
-                self._cache[bkey(b)] = (b._version, o.reshape(-1), weakref.ref(b))
-        return [self._cache[bkey(b)][1] for b in biases]
+        return self._build(biases, lambda b, tr: (id(b), "scaled-bias", False, rows, self.row_scale), torch.float32, rows=lambda b: rows,
+                           src=lambda b: b.detach().reshape(-1, 1), view=lambda o: o.reshape(-1))
 
     def clear(self):
         self._cache.clear()
         self.epoch += 1
         self.builds += 1
+
+
+def _block_sites(reg, i: int):
+    """Block i's regularised sites (include/maest_hip.h: site 8 * i + k), (site, rate) or None each; None for a block with none, which
+    keeps the launches of an unregularised forward.  reg: the forward's drop rate `p` and per-block drop-path rates `dpr`, or None."""
+    if reg is None or not (reg["p"] > 0 or reg["dpr"][i] > 0):
+        return None
+    elem = lambda k: (8 * i + k, reg["p"]) if reg["p"] > 0 else None
+    path = lambda k: (8 * i + k, reg["dpr"][i]) if reg["dpr"][i] > 0 else None
+    return dict(elem_a=elem(0), path_a=path(1), elem_h=elem(2), elem_m=elem(3), path_m=path(4))
 
 
 def _split_k(n_out: int, k_out: int, tokens: int) -> int:
@@ -305,19 +304,16 @@ class _Engine:
         # bf16 mode: scale * log2(e) of the softmax rides in the q rows of the qkv projections' forward operand copies (and in the q part
         # of a copy of their biases), so the attention kernels read q' = scale * log2(e) * q rounded ONCE (MAEST_BF16_QS: the forward
         # takes its fragments straight from the rows, forward and backward exponentiate the same operand product)
-        self.fold_qscale = True
-        self.persistent_gemm = True      # see _gemm_form
+        self.fold_qscale = os.environ.get("MAEST_FOLD_QSCALE", "1") != "0"
+        self.persistent_gemm = os.environ.get("MAEST_PERSISTENT_GEMM", "1") != "0"      # see _gemm_form
         # "bf16x3" forwards that record no graph (the default evaluation mode): the three-term split product of the qkv / proj / fc1
         # linears runs as ONE bf16 GEMM over 3 K on the fast bf16 kernel -- LayerNorm and the attention forward write their fp32
         # results as [ hi | hi | lo ] bf16 rows (MAEST_SPLIT3_A), the weights are kept as [ hi | lo | hi ] rows (MAEST_SPLIT3_B):
         # the same three products per k as MAEST_F32X3, accumulated in fp32; the fc1 GEMM writes gelu(.) in that row form from its
         # epilogue (large M: the one-wave-per-SIMD kernel), so fc2 follows suit.  The last block's head-token rows (and small M) stay
         # on the per-chunk split kernels.  Same-box at configs[1]: profiles/r05_ab_x3_fast.txt
-        self.x3_fast = True
-        # (A/B switches of the three engine-level choices above: MAEST_FOLD_QSCALE / MAEST_PERSISTENT_GEMM / MAEST_X3_FAST = 0 turn one off)
-        self.fold_qscale = os.environ.get("MAEST_FOLD_QSCALE", "1") != "0"
-        self.persistent_gemm = os.environ.get("MAEST_PERSISTENT_GEMM", "1") != "0"
         self.x3_fast = os.environ.get("MAEST_X3_FAST", "1") != "0"
+        # (A/B switches of the three engine-level choices above: MAEST_FOLD_QSCALE / MAEST_PERSISTENT_GEMM / MAEST_X3_FAST = 0 turn one off)
         # bf16 mode: residual adds ride in the LayerNorm that follows (True, see forward) or in the proj / fc2 GEMMs' fp32 RESIDUAL epilogue (False)
         # 1: both adds of a block in the LayerNorms; 0: both in GEMM epilogues; 2: proj's in norm2, fc2's in its epilogue.  Training forwards
         # (a graph is recorded) and evaluation forwards choose separately
@@ -418,7 +414,7 @@ class _Engine:
         i's qkv GEMM, with what an attention kernel needs to read that tensor; None: exactly the launches below.
         tap_x (maest_amd/hidden.py: the hidden states): called as tap_x(i, x) with block i's output stream -- fp32 [B * N, 768], which no later
         launch writes -- as soon as that tensor exists: behind the next block's first LayerNorm pass where that pass carries the fc2 add
-        (`pending`), else behind block i's fc2 GEMM, for the last block of the pass behind the loop (there [B * 2, 768] when that block ran
+        (`carry`), else behind block i's fc2 GEMM, for the last block of the pass behind the loop (there [B * 2, 768] when that block ran
         on the head rows); None: exactly the launches below.  full_last: the last block runs complete whatever head_tail says.
         explain (MAEST.attention_relevance, with save): the activations are kept for a backward that updates no weight -- the
         operand copies are cached as an evaluation forward caches them, and no dropout / drop-path is drawn (the step counter stays)."""
@@ -513,116 +509,106 @@ class _Engine:
         mode = self.split_add if save else self.split_add_eval
         split_add = dt != torch.float32 and mode in (1, 2)
         split_add_fc2 = dt != torch.float32 and mode == 1
-        pending = None            # delta of the previous block's fc2, to be added by this block's norm1
-        pending_reg = None        # ... and the (element, path) sites of that branch when it is regularised
+
+        def norm(ln, x, add=None, out_dtype=dt, rows=N):
+            """LayerNorm `ln` of the stream x -> (x, y, mean, rstd), the statistics None when nothing is saved.  add = (delta, sites): the
+            delta of a residual branch joins the stream in the same pass -- x comes back as the new stream --, times the branch multiplier
+            of sites = (elem, path) where the branch is regularised (rows: the rows of a clip in x)."""
+            if add is None:
+                r = ops.layernorm_fwd(x, ln.weight, ln.bias, ln.eps, out_dtype, save_stats=save)
+                return (x, *r) if save else (x, r, None, None)
+            delta, sites = add
+            if sites is None:
+                r = ops.add_layernorm_fwd(x, delta, ln.weight, ln.bias, ln.eps, dt, save_stats=save)
+            else:
+                r = ops.drop_add_layernorm_fwd(x, delta, ln.weight, ln.bias, ln.eps, dt, B, N, rows, *sites, reg["snap"], save_stats=save)
+            return r if save else (*r, None, None)
+
+        def linear(i, name, a, fast, **kw):
+            """The GEMM of block i's linear `name` on a: fast -- the split path of "bf16x3" evaluation, a in MAEST_SPLIT3_A rows -- against the
+            MAEST_SPLIT3_B copy of the weight as one bf16 GEMM over 3 K; else against the mode's operand copy, in the mode's product."""
+            lin = getattr(m.blocks[i].attn if name in ("qkv", "proj") else m.blocks[i].mlp, name)
+            bias = qkv_bias[i] if name == "qkv" else lin.bias
+            if fast:
+                return ops.gemm_nt(a, w3[(i, name)], bias, split3=True, **kw)
+            return gemm_nt(a, W.get(lin.weight, dt), bias, **kw)
+
+        carry = None              # what the previous block left for this block's norm1 to add: (delta of its fc2, its sites or None)
         for i in range(nblocks):
             blk = m.blocks[i]
-            # this block's regularised sites, (site, rate) or None each (include/maest_hip.h); a block with none keeps the path below
-            br = None
-            if reg is not None and (reg["p"] > 0 or reg["dpr"][i] > 0):
-                pe, pp = reg["p"], reg["dpr"][i]
-                br = dict(elem_a=(8 * i, pe) if pe > 0 else None, path_a=(8 * i + 1, pp) if pp > 0 else None,
-                          elem_h=(8 * i + 2, pe) if pe > 0 else None, elem_m=(8 * i + 3, pe) if pe > 0 else None,
-                          path_m=(8 * i + 4, pp) if pp > 0 else None)
-            carried = pending is not None      # this block's norm1 pass completes the previous block's output stream
-            if pending is not None and pending_reg is not None:
-                r = ops.drop_add_layernorm_fwd(x, pending, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, B, N, N,
-                                               pending_reg[0], pending_reg[1], reg["snap"], save_stats=save)
-                x, ln1 = r[0], r[1]
-                mean1, rstd1 = (r[2], r[3]) if save else (None, None)
-                pending = pending_reg = None
-            elif pending is not None:
-                r = ops.add_layernorm_fwd(x, pending, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, dt, save_stats=save)
-                x, ln1 = r[0], r[1]
-                mean1, rstd1 = (r[2], r[3]) if save else (None, None)
-                pending = None
-            else:
-                r = ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, ops.SPLIT3 if fast3 else dt, save_stats=save)
-                ln1, mean1, rstd1 = r if save else (r, None, None)
-            if tap_x is not None and carried:
-                tap_x(i - 1, x)
-            if fast3:
-                qkv = ops.gemm_nt(ln1, w3[(i, "qkv")], qkv_bias[i], out_dtype=torch.float32, split3=True)
-            else:
-                qkv = gemm_nt(ln1, W.get(blk.attn.qkv.weight, dt), qkv_bias[i], out_dtype=dt)
-            if tap is not None:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
-                tap(i, qkv, (B, N, scale, x3m, qs))
+            # The block's three choices, made here and carried out below.  (1) Is a branch regularised: br, its sites (a block with none
+            # keeps the launches of an unregularised forward).  (2) Which operand copy the GEMMs take: `fast3` for norm1 -> qkv, which
+            # always run on every row, `fast` for the rest of the block.  (3) Where the two residual adds ride: in the LayerNorm pass that
+            # follows -- a regularised branch in every numeric mode: the GEMM emits its output with the bias-only epilogue and the add
+            # rides there with the branch multiplier -- or in the GEMM's fp32 RESIDUAL epilogue.
+            br = _block_sites(reg, i)
             tail = self.head_tail and not full_last and stop_block < 0 and i == nblocks - 1
             # (training needs the backward kernel that honours the restriction; otherwise the attention stays complete
             # and only the per-token part of the block is restricted)
             q_rows = HEAD_TOKENS if tail and (not save or ops.attn_bwd_rows_supported(dt, N)) else None
-            fast_blk = fast3 and not tail and not (i == stop_block and return_self_attention)
-            r = ops.attn_fwd(qkv, B, N, scale, save_lse=save, q_rows=q_rows, x3=x3m, q_prescaled=qs, out_split3=fast_blk, n_tok=n_tok)
+            attn_exit = i == stop_block and return_self_attention
+            fast = fast3 and not tail and not attn_exit
+            proj_add_in_norm2 = br is not None or split_add
+            fc2_add_in_next_norm1 = i + 1 < nblocks and (br is not None or split_add_fc2)
+            rpc = HEAD_TOKENS if tail else N      # rows of a clip in this block's per-token buffers
+
+            # norm1 (this pass completes the previous block's output stream where it carries that block's fc2 add) -> qkv -> attention
+            x, ln1, mean1, rstd1 = norm(blk.norm1, x, carry, out_dtype=ops.SPLIT3 if fast3 else dt)
+            if tap_x is not None and carry is not None:
+                tap_x(i - 1, x)
+            carry = None
+            qkv = linear(i, "qkv", ln1, fast3, out_dtype=torch.float32 if fast3 else dt)
+            if tap is not None:      # (the qkv of the last block is complete even when the rest of it runs on the head rows)
+                tap(i, qkv, (B, N, scale, x3m, qs))
+            r = ops.attn_fwd(qkv, B, N, scale, save_lse=save, q_rows=q_rows, x3=x3m, q_prescaled=qs, out_split3=fast, n_tok=n_tok)
             ao, lse = r if save else (r, None)
             ao_full, x_full, Mb = ao, x, M
             if tail:      # from here on the block lives on [B * 2, 768]
                 ao = ops.gather_head_rows(ao, B, N, HEAD_TOKENS)
                 x = ops.gather_head_rows(x, B, N, HEAD_TOKENS)
                 Mb = B * HEAD_TOKENS
-            if i == stop_block and return_self_attention:
-                # Block.forward(..., return_self_attention=True) returns attn(norm1(x)) (maest.py:414-416)
-                a = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=torch.float32)
+            if save:      # (the rest of the block adds what it makes; the return_self_attention exit keeps this subset)
+                s = dict(x=x_full, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, ao=ao, lse=lse, tail=tail, ao_full=ao_full, q_rows=q_rows,
+                         reg=br, rpc=rpc)
+                ctx["blocks"].append(s)
+            if attn_exit:
+                # Block.forward(..., return_self_attention=True) returns attn(norm1(x)) (maest.py:414-416); the backward of this block
+                # starts at the proj GEMM: norm2 / MLP are not part of the output
+                a = linear(i, "proj", ao, False, out_dtype=torch.float32)
                 if br is not None and br["elem_a"] is not None:      # proj_drop is part of Attention.forward; drop-path is not
                     ops.dropout_(a, None, B, N, N, *br["elem_a"], reg["snap"])
-                if save:      # (the backward of this block starts at the proj GEMM: norm2 / MLP are not part of the output)
-                    ctx["blocks"].append(dict(x=x_full, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, ao=ao, lse=lse, tail=False,
-                                              ao_full=ao_full, q_rows=None, reg=br, rpc=N))
                 return ops.embed_pool(a.reshape(B, N, EMBED_DIM)), ctx
-            rpc = HEAD_TOKENS if tail else N      # rows of a clip in this block's per-token buffers
-            if br is not None:
-                # the split form in every numeric mode: proj emits its output with the bias-only epilogue and the residual add rides, with
-                # the branch multiplier, in the LayerNorm pass that follows
-                d1 = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=dt)
-                r = ops.drop_add_layernorm_fwd(x, d1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, B, N, rpc,
-                                               br["elem_a"], br["path_a"], reg["snap"], save_stats=save)
-                x1, ln2 = r[0], r[1]
-                mean2, rstd2 = (r[2], r[3]) if save else (None, None)
-            elif split_add:
-                d1 = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=dt)
-                r = ops.add_layernorm_fwd(x, d1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save_stats=save)
-                x1, ln2 = r[0], r[1]
-                mean2, rstd2 = (r[2], r[3]) if save else (None, None)
-            elif fast_blk:
-                x1 = ops.gemm_nt(ao, w3[(i, "proj")], blk.attn.proj.bias, out_dtype=torch.float32, epi=ops.EPI_RESIDUAL, aux_in=x, split3=True)
-                ln2 = ops.layernorm_fwd(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, ops.SPLIT3)
-                mean2 = rstd2 = None
+
+            # proj -> norm2
+            if proj_add_in_norm2:
+                d1 = linear(i, "proj", ao, False, out_dtype=dt)
+                x1, ln2, mean2, rstd2 = norm(blk.norm2, x, (d1, None if br is None else (br["elem_a"], br["path_a"])), rows=rpc)
             else:
-                x1 = gemm_nt(ao, W.get(blk.attn.proj.weight, dt), blk.attn.proj.bias, out_dtype=torch.float32,
-                                 epi=ops.EPI_RESIDUAL, aux_in=x)
-                r = ops.layernorm_fwd(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, dt, save_stats=save)
-                ln2, mean2, rstd2 = r if save else (r, None, None)
-            h = torch.empty((Mb, blk.mlp.fc1.out_features), dtype=dt, device=x.device) if save else None
-            fast_fc2 = fast_blk and ops.gemm_split3_out_fast(Mb, blk.mlp.fc1.out_features, 3 * EMBED_DIM)
-            if fast_fc2:      # gelu(fc1) leaves the GEMM epilogue as [ hi | hi | lo ] rows: fc2 takes the 3 K bf16 GEMM as well
-                g = ops.gemm_nt(ln2, w3[(i, "fc1")], blk.mlp.fc1.bias, out_dtype=ops.SPLIT3, epi=ops.EPI_GELU, split3=True)
-            elif fast_blk:    # (small M: an fp32 output and the per-chunk split kernel for fc2)
-                g = ops.gemm_nt(ln2, w3[(i, "fc1")], blk.mlp.fc1.bias, out_dtype=torch.float32, epi=ops.EPI_GELU, split3=True)
-            else:
-                g = gemm_nt(ln2, W.get(blk.mlp.fc1.weight, dt), blk.mlp.fc1.bias, out_dtype=dt, epi=ops.EPI_GELU,
-                            aux_out=h)
+                x1 = linear(i, "proj", ao, fast, out_dtype=torch.float32, epi=ops.EPI_RESIDUAL, aux_in=x)
+                x1, ln2, mean2, rstd2 = norm(blk.norm2, x1, out_dtype=ops.SPLIT3 if fast else dt)
+
+            # fc1: on the fast path gelu(fc1) leaves the GEMM epilogue as [ hi | hi | lo ] rows where that epilogue is the fast one, and fc2
+            # takes the 3 K bf16 GEMM as well (small M: an fp32 output and the per-chunk split kernel for fc2)
+            H = blk.mlp.fc1.out_features
+            h = torch.empty((Mb, H), dtype=dt, device=x.device) if save else None
+            fast_fc2 = fast and ops.gemm_split3_out_fast(Mb, H, 3 * EMBED_DIM)
+            g = linear(i, "fc1", ln2, fast, out_dtype=(ops.SPLIT3 if fast_fc2 else torch.float32) if fast else dt, epi=ops.EPI_GELU, aux_out=h)
             if br is not None and br["elem_h"] is not None:
                 # Mlp.drop behind fc1 (models/maest.py:205), on gelu(.) and on the saved gelu'(.): the EPI_MUL dgrad then carries the mask
                 ops.dropout_(g, h, B, N, rpc, *br["elem_h"], reg["snap"])
             if save:
-                ctx["blocks"].append(dict(x=x_full, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, ao=ao, lse=lse, x1=x1,
-                                          mean2=mean2, rstd2=rstd2, ln2=ln2, h=h, g=g, tail=tail, ao_full=ao_full,
-                                          q_rows=q_rows, reg=br, rpc=rpc))
-            if br is not None:
-                d2 = gemm_nt(g, W.get(blk.mlp.fc2.weight, dt), blk.mlp.fc2.bias, out_dtype=dt)
-                if i + 1 < nblocks:      # the next block's norm1 carries the add
-                    pending, pending_reg, x = d2, (br["elem_m"], br["path_m"]), x1
-                else:
-                    x = ops.drop_add(x1, d2, B, N, rpc, br["elem_m"], br["path_m"], reg["snap"])
-            elif split_add_fc2 and i + 1 < nblocks:
-                pending = gemm_nt(g, W.get(blk.mlp.fc2.weight, dt), blk.mlp.fc2.bias, out_dtype=dt)
-                x = x1
-            elif fast_blk and g.dtype == torch.bfloat16:     # (split rows from the fc1 epilogue)
-                x = ops.gemm_nt(g, w3[(i, "fc2")], blk.mlp.fc2.bias, out_dtype=torch.float32, epi=ops.EPI_RESIDUAL, aux_in=x1, split3=True)
-            else:             # last block of this pass: nothing follows that could carry the add
-                x = gemm_nt(g, W.get(blk.mlp.fc2.weight, dt), blk.mlp.fc2.bias, out_dtype=torch.float32,
-                                epi=ops.EPI_RESIDUAL, aux_in=x1)
-            if tap_x is not None and pending is None and i + 1 < nblocks:
-                tap_x(i, x)
+                s.update(x1=x1, mean2=mean2, rstd2=rstd2, ln2=ln2, h=h, g=g)
+
+            # fc2: its add rides in the next block's norm1, in the GEMM's epilogue, or -- a regularised last block of the pass, which
+            # nothing follows that could carry it -- in a pass of its own
+            if fc2_add_in_next_norm1:
+                x, carry = x1, (linear(i, "fc2", g, False, out_dtype=dt), None if br is None else (br["elem_m"], br["path_m"]))
+            elif br is not None:
+                x = ops.drop_add(x1, linear(i, "fc2", g, False, out_dtype=dt), B, N, rpc, br["elem_m"], br["path_m"], reg["snap"])
+            else:
+                x = linear(i, "fc2", g, fast_fc2, out_dtype=torch.float32, epi=ops.EPI_RESIDUAL, aux_in=x1)
+                if tap_x is not None and i + 1 < nblocks:
+                    tap_x(i, x)
         if tap_x is not None:
             tap_x(nblocks - 1, x)
         xb = x.reshape(B, -1, EMBED_DIM)          # [B, N, 768], or [B, 2, 768] behind a restricted last block
@@ -631,22 +617,19 @@ class _Engine:
         r = ops.head_pool_fwd(xb, m.norm.weight, m.norm.bias, m.norm.eps, save_stats=save)
         cls, dist, feat = r[:3]
         hn, hw = m.head[0], m.head[1]
+        if m.distilled_type not in ("mean", "separated"):
+            raise NotImplementedError(f"distilled_type={m.distilled_type!r}")
+        # the head reads the features ("mean") or the cls token ("separated": the dist token goes through head_dist, a bare Linear)
+        _, hl, hmean, hrstd = norm(hn, feat if m.distilled_type == "mean" else cls)
+        logits = gemm_nt(hl, W.get(hw.weight, dt), hw.bias, out_dtype=torch.float32)
         if m.distilled_type == "mean":
-            r2 = ops.layernorm_fwd(feat, hn.weight, hn.bias, hn.eps, dt, save_stats=save)
-            hl, hmean, hrstd = r2 if save else (r2, None, None)
-            logits = gemm_nt(hl, W.get(hw.weight, dt), hw.bias, out_dtype=torch.float32)
             outs = (logits, feat)
-        elif m.distilled_type == "separated":
-            r2 = ops.layernorm_fwd(cls, hn.weight, hn.bias, hn.eps, dt, save_stats=save)
-            hl, hmean, hrstd = r2 if save else (r2, None, None)
-            logits = gemm_nt(hl, W.get(hw.weight, dt), hw.bias, out_dtype=torch.float32)
+        else:
             dlp = dist if dt == torch.float32 else ops.cast_weights(dist, dt)[0]
             logits_d = gemm_nt(dlp, W.get(m.head_dist.weight, dt), m.head_dist.bias, out_dtype=torch.float32)
             outs = (logits, logits_d, feat)
             if save:
                 ctx["dist_lp"] = dlp
-        else:
-            raise NotImplementedError(f"distilled_type={m.distilled_type!r}")
         if save:
             ctx.update(x_final=xb, fmean=r[3], frstd=r[4], cls=cls, dist=dist, feat=feat, hl=hl, hmean=hmean,
                        hrstd=hrstd)
@@ -767,6 +750,20 @@ class _Engine:
             done(name_w, gw if w_shape is None else gw.view(w_shape))
             done(name_b, gb)
 
+        def norm_done(prefix, bufs):
+            done(prefix + ".weight", bufs[0])
+            done(prefix + ".bias", bufs[1])
+
+        def ln_bwd(prefix, norm, dy, x, mean, rstd, dres, *, lp=True, head_tokens=None, bufs=None):
+            """The backward of LayerNorm `prefix` -> (dx fp32, dx in the operand dtype: the same tensor in the fp32 modes, None without `lp`).
+            Its gamma / beta sums land where norm_bufs says and are reported at once -- or in `bufs`, which the caller reports."""
+            gw, gb = bufs or norm_bufs(prefix)
+            dx, dx_lp = ops.layernorm_bwd(dy, x, norm.weight, mean, rstd, dres, gw, gb, lp_dtype=dt if lp and dt != torch.float32 else None,
+                                          head_tokens=head_tokens)
+            if bufs is None:
+                norm_done(prefix, (gw, gb))
+            return dx, (dx if lp and dt == torch.float32 else dx_lp)
+
         if stop >= 0:
             # truncated forward: the head, the final norm and the blocks above `stop` never ran -- nothing of theirs runs here
             if sink is not None:
@@ -784,6 +781,8 @@ class _Engine:
             if d_emb is None:
                 d_emb = torch.zeros((B, 3 * EMBED_DIM), dtype=torch.float32, device=dev)
             dx, dx_lp = ops.embed_pool_bwd(d_emb.float().contiguous(), N, lp_dtype=dt)
+            if dx_lp is None:      # (the fp32 modes)
+                dx_lp = dx
         else:
             C = m.head[1].out_features
             cpad = ops.round_up(C, 64)
@@ -795,38 +794,26 @@ class _Engine:
                 wt = W.get(lin.weight, dt, transposed=True, pad_cols_to=64)          # [768, cpad]
                 return gemm_nt(dl, wt, None, out_dtype=out_dtype, M=B, N=EMBED_DIM, K=cpad)
 
+            # "mean": the head reads the features, whose own output gradient rides in its LayerNorm backward as the residual;
+            # "separated": it reads the cls token, and head_dist the dist token
+            sep = m.distilled_type != "mean"
+            dlogits, dlogits_d, dfeat_out = grads_out if sep else (grads_out[0], None, grads_out[1])
+            dfeat = None if dfeat_out is None else dfeat_out.contiguous()
             d_cls = d_dist = None
-            g_h0w, g_h0b = norm_bufs("head.0")
-            if m.distilled_type == "mean":
-                dlogits, dfeat_out = grads_out
-                dfeat = None
-                if dlogits is not None:
-                    dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
-                    dres = None if dfeat_out is None else dfeat_out.contiguous()
-                    dfeat, _ = ops.layernorm_bwd(dhl, ctx["feat"], hn.weight, ctx["hmean"], ctx["hrstd"], dres,
-                                                 g_h0w, g_h0b)
-                elif dfeat_out is not None:
-                    dfeat = dfeat_out.contiguous()
-            else:
-                dlogits, dlogits_d, dfeat_out = grads_out
-                dfeat = None if dfeat_out is None else dfeat_out.contiguous()
-                if dlogits is not None:
-                    dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
-                    d_cls, _ = ops.layernorm_bwd(dhl, ctx["cls"], hn.weight, ctx["hmean"], ctx["hrstd"], None,
-                                                 g_h0w, g_h0b)
-                if dlogits_d is not None:
-                    # head_dist is a bare Linear: its input gradient feeds head_pool_bwd directly, in fp32
-                    d_dist = head_linear_bwd(dlogits_d.contiguous(), ctx["dist_lp"], m.head_dist, "head_dist", torch.float32)
-            done("head.0.weight", g_h0w)
-            done("head.0.bias", g_h0b)
-            g_nw, g_nb = norm_bufs("norm")
-            dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"],
-                                   g_nw, g_nb).reshape(-1, EMBED_DIM)
-            done("norm.weight", g_nw)
-            done("norm.bias", g_nb)
+            h0 = norm_bufs("head.0")
+            if dlogits is not None:
+                dhl = head_linear_bwd(dlogits.contiguous(), ctx["hl"], hw, "head.1", dt)
+                d, _ = ln_bwd("head.0", hn, dhl, ctx["cls" if sep else "feat"], ctx["hmean"], ctx["hrstd"], None if sep else dfeat,
+                              lp=False, bufs=h0)
+                d_cls, dfeat = (d, dfeat) if sep else (None, d)
+            if dlogits_d is not None:
+                # head_dist is a bare Linear: its input gradient feeds head_pool_bwd directly, in fp32
+                d_dist = head_linear_bwd(dlogits_d.contiguous(), ctx["dist_lp"], m.head_dist, "head_dist", torch.float32)
+            norm_done("head.0", h0)
+            nb = norm_bufs("norm")
+            dx = ops.head_pool_bwd(d_cls, d_dist, dfeat, ctx["x_final"], m.norm.weight, ctx["fmean"], ctx["frstd"], *nb).reshape(-1, EMBED_DIM)
+            norm_done("norm", nb)
             dx_lp = dx if dt == torch.float32 else ops.cast_weights(dx, dt)[0]
-        if dt == torch.float32:
-            dx_lp = dx
 
         reg = ctx.get("reg")
 
@@ -857,13 +844,7 @@ class _Engine:
                 # fc1
                 wgrad(p + "mlp.fc1.weight", p + "mlp.fc1.bias", dh, s["ln2"], H, EMBED_DIM)
                 dln2 = gemm_nt(dh, W.get(blk.mlp.fc1.weight, dt, transposed=True), None, out_dtype=dt)
-                gw, gb = norm_bufs(p + "norm2")
-                dx1, dx1_lp = ops.layernorm_bwd(dln2, s["x1"], blk.norm2.weight, s["mean2"], s["rstd2"], dx, gw, gb,
-                                                lp_dtype=None if dt == torch.float32 else dt)
-                done(p + "norm2.weight", gw)
-                done(p + "norm2.bias", gb)
-                if dt == torch.float32:
-                    dx1_lp = dx1
+                dx1, dx1_lp = ln_bwd(p + "norm2", blk.norm2, dln2, s["x1"], s["mean2"], s["rstd2"], dx)
                 dres1 = dx1
                 if br is not None:
                     dx1_lp = enter(dx1, dx1_lp, br["elem_a"], br["path_a"], rpc)
@@ -891,14 +872,8 @@ class _Engine:
                                 x3=x3m, delta=delta, q_prescaled=qs)
             wgrad(p + "attn.qkv.weight", p + "attn.qkv.bias", dqkv, s["ln1"], 3 * EMBED_DIM, EMBED_DIM)
             dln1 = gemm_nt(dqkv, W.get(blk.attn.qkv.weight, dt, transposed=True), None, out_dtype=dt)
-            gw, gb = norm_bufs(p + "norm1")
-            dx, dx_lp = ops.layernorm_bwd(dln1, s["x"], blk.norm1.weight, s["mean1"], s["rstd1"], dres1, gw, gb,
-                                          lp_dtype=None if dt == torch.float32 else dt,
-                                          head_tokens=(N, HEAD_TOKENS) if s["tail"] else None)
-            done(p + "norm1.weight", gw)
-            done(p + "norm1.bias", gb)
-            if dt == torch.float32:
-                dx_lp = dx
+            dx, dx_lp = ln_bwd(p + "norm1", blk.norm1, dln1, s["x"], s["mean1"], s["rstd1"], dres1,
+                               head_tokens=(N, HEAD_TOKENS) if s["tail"] else None)
             s.clear()  # release this block's activations
 
         if first is not None:

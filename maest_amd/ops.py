@@ -390,6 +390,12 @@ def _attn_flops_lens(n_tok, N, q_rows, per_pair):
     return per_pair * HEADS * int((nq * n).sum()) * HEAD_DIM
 
 
+def _attn_code(qkv, x3: bool, q_prescaled):
+    """dtype code of the qkv operand of an attention entry point: _mm_code, or -- q_prescaled (bf16 only) -- MAEST_BF16_QS."""
+    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    return BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)
+
+
 def attn_fwd(qkv: torch.Tensor, B: int, N: int, scale: float, save_lse=False, q_rows=None, x3: bool = False, q_prescaled=False,
              out_split3=False, n_tok=None):
     """q_rows: only the first q_rows queries of every clip are wanted (rows beyond the 32-row tile that holds them are
@@ -400,14 +406,15 @@ def attn_fwd(qkv: torch.Tensor, B: int, N: int, scale: float, save_lse=False, q_
     if n_tok is not None:
         assert not save_lse, "n_tok (MAEST_ATTN_LENS) saves no lse"
         assert n_tok.dtype == torch.int32 and tuple(n_tok.shape) == (B,) and n_tok.device == qkv.device
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    code = _attn_code(qkv, x3, q_prescaled)
     assert qkv.shape == (B * N, 3 * EMBED)
     # out_split3 (x3 mode): the fp32 result leaves as MAEST_SPLIT3_A rows, bf16 [B * N, 3 * 768] -- the A operand of the proj GEMM
     assert not out_split3 or (x3 and qkv.dtype == torch.float32)
     out = (torch.empty((B * N, 3 * EMBED), dtype=torch.bfloat16, device=qkv.device) if out_split3
            else torch.empty((B * N, EMBED), dtype=qkv.dtype, device=qkv.device))
     lse = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device) if save_lse else None
-    code = F32X3_A3 if out_split3 else (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3))
+    if out_split3:
+        code = F32X3_A3
     if n_tok is not None:
         _timed_call("maest_attn_fwd", _attn_flops_lens(n_tok, N, q_rows, 4.0), _p(qkv), _p(out), _p(n_tok), B, N, code | _lib.ATTN_LENS, scale,
                     N if q_rows is None else q_rows, _s(qkv), _entry="maest_attn_fwd_rows")
@@ -422,34 +429,41 @@ def attn_probs(qkv: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3:
     keys, [B, 12, q_rows, N] -- or, head_mean, their mean over the heads, [B, q_rows, N] = (((p0 + p1) + ...) + p11) * fp32(1 / 12).
     MAEST_ATTN_PROBS (| MAEST_ATTN_PROBS_MEAN) on maest_attn_fwd_rows; x3 / q_prescaled as in attn_fwd."""
     _chk(qkv)
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    code = _attn_code(qkv, x3, q_prescaled) | _lib.ATTN_PROBS | (_lib.ATTN_PROBS_MEAN if head_mean else 0)
     assert qkv.shape == (B * N, 3 * EMBED)
     q_rows = N if q_rows is None else q_rows
     out = torch.empty((B, q_rows, N) if head_mean else (B, HEADS, q_rows, N), dtype=torch.float32, device=qkv.device)
-    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_PROBS | (_lib.ATTN_PROBS_MEAN if head_mean else 0)
     # (work: the score product, formed twice)
     _timed_call("maest_attn_probs", _attn_flops(B, N, q_rows, 4.0), _p(qkv), _p(out), None, B, N, code, scale, q_rows, _s(qkv),
                 _entry="maest_attn_fwd_rows")
     return out
 
 
+def _attn_pool(grad: bool, heads: bool, qkv, dout, w, B, N, scale, q_rows, x3, q_prescaled):
+    """The body of attn_apply / attn_relevance (grad: the gradient-weighted form, which reads dout) / attn_apply_heads /
+    attn_relevance_heads (heads: the heads kept apart, [B, 12, R, N] instead of their mean [B, R, N])."""
+    _chk(qkv, dout, w)
+    code = _attn_code(qkv, x3, q_prescaled)
+    assert qkv.shape == (B * N, 3 * EMBED)
+    if grad:
+        assert dout.dtype == qkv.dtype and dout.shape == (B * N, EMBED), (dout.dtype, tuple(dout.shape))
+    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
+    R = w.shape[1]
+    q_rows = N if q_rows is None else q_rows
+    y = torch.empty((B, HEADS, R, N) if heads else (B, R, N), dtype=torch.float32, device=qkv.device)
+    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
+    code |= (_lib.ATTN_APPLY | (_lib.ATTN_APPLY_GRAD if grad else 0) | (_lib.ATTN_APPLY_HEADS if heads else 0) | _lib.attn_apply_rows(R))
+    # (work: the score product, formed twice, and -- gradient-weighted -- the dP product)
+    _timed_call("maest_attn_" + ("relevance" if grad else "apply") + ("_heads" if heads else ""), _attn_flops(B, N, q_rows, 6.0 if grad else 4.0),
+                _p(qkv), _p(dout), _p(w), None, _p(lse2), _p(y), B, N, code, scale, q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
+    return y
+
+
 def attn_apply(qkv: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False, q_prescaled=False) -> torch.Tensor:
     """Weighted attention pooling, the step of attention rollout: Y[b, r, k] = sum_{q < q_rows} w[b, r, q] * mean_h softmax(scale q k^T)[b, h, q, k]
     for R <= 8 fp32 weight rows w [B, R, N] (columns >= q_rows are not read) -> fp32 [B, R, N], heads summed in ascending order and scaled by
     fp32(1 / 12).  No N x N tensor is written.  MAEST_ATTN_APPLY on maest_attn_bwd_rows; x3 / q_prescaled as in attn_fwd."""
-    _chk(qkv, w)
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
-    assert qkv.shape == (B * N, 3 * EMBED)
-    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
-    R = w.shape[1]
-    q_rows = N if q_rows is None else q_rows
-    y = torch.empty((B, R, N), dtype=torch.float32, device=qkv.device)
-    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
-    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.attn_apply_rows(R)
-    # (work: the score product, formed twice)
-    _timed_call("maest_attn_apply", _attn_flops(B, N, q_rows, 4.0), _p(qkv), None, _p(w), None, _p(lse2), _p(y), B, N, code, scale, q_rows,
-                _s(qkv), _entry="maest_attn_bwd_rows")
-    return y
+    return _attn_pool(False, False, qkv, None, w, B, N, scale, q_rows, x3, q_prescaled)
 
 
 def attn_relevance(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False,
@@ -458,20 +472,7 @@ def attn_relevance(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, B: in
     mean_h max(P_h[q, k] * dP_h[q, k], 0), P = softmax(scale q k^T) and dP_h[q, k] = dout_h[q] . v_h[k] the gradient of the scalar behind
     `dout` ([B * N, 768] of qkv's type: d / d(attn @ v); rows >= q_rows of a clip are not read) with respect to P.  w fp32 [B, R, N], R <= 8
     -> fp32 [B, R, N]; no N x N tensor is written.  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD on maest_attn_bwd_rows."""
-    _chk(qkv, dout, w)
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
-    assert qkv.shape == (B * N, 3 * EMBED)
-    assert dout.dtype == qkv.dtype and dout.shape == (B * N, EMBED), (dout.dtype, tuple(dout.shape))
-    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
-    R = w.shape[1]
-    q_rows = N if q_rows is None else q_rows
-    y = torch.empty((B, R, N), dtype=torch.float32, device=qkv.device)
-    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
-    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.ATTN_APPLY_GRAD | _lib.attn_apply_rows(R)
-    # (work: the score product, formed twice, and the dP product)
-    _timed_call("maest_attn_relevance", _attn_flops(B, N, q_rows, 6.0), _p(qkv), _p(dout), _p(w), None, _p(lse2), _p(y), B, N, code, scale,
-                q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
-    return y
+    return _attn_pool(True, False, qkv, dout, w, B, N, scale, q_rows, x3, q_prescaled)
 
 
 def attn_apply_heads(qkv: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False,
@@ -479,19 +480,7 @@ def attn_apply_heads(qkv: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: 
     """attn_apply with the heads kept apart: Y[b, h, r, k] = sum_{q < q_rows} w[b, r, q] * softmax(scale q k^T)[b, h, q, k] -> fp32
     [B, 12, R, N], per head the very arithmetic of attn_apply, so heads_mean(Y) is attn_apply's result bit for bit.  No N x N tensor is
     written.  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_HEADS on maest_attn_bwd_rows; the arguments are attn_apply's."""
-    _chk(qkv, w)
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
-    assert qkv.shape == (B * N, 3 * EMBED)
-    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
-    R = w.shape[1]
-    q_rows = N if q_rows is None else q_rows
-    y = torch.empty((B, HEADS, R, N), dtype=torch.float32, device=qkv.device)
-    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
-    code = (BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.ATTN_APPLY_HEADS | _lib.attn_apply_rows(R)
-    # (work: the score product, formed twice)
-    _timed_call("maest_attn_apply_heads", _attn_flops(B, N, q_rows, 4.0), _p(qkv), None, _p(w), None, _p(lse2), _p(y), B, N, code, scale,
-                q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
-    return y
+    return _attn_pool(False, True, qkv, None, w, B, N, scale, q_rows, x3, q_prescaled)
 
 
 def attn_relevance_heads(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor, B: int, N: int, scale: float, q_rows=None, x3: bool = False,
@@ -499,21 +488,7 @@ def attn_relevance_heads(qkv: torch.Tensor, dout: torch.Tensor, w: torch.Tensor,
     """attn_relevance with the heads kept apart: Y[b, h, r, k] = sum_{q < q_rows} w[b, r, q] * max(P_h[q, k] * dP_h[q, k], 0) -> fp32
     [B, 12, R, N]; heads_mean(Y) is attn_relevance's result bit for bit.  MAEST_ATTN_APPLY | MAEST_ATTN_APPLY_GRAD |
     MAEST_ATTN_APPLY_HEADS on maest_attn_bwd_rows; the arguments are attn_relevance's."""
-    _chk(qkv, dout, w)
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
-    assert qkv.shape == (B * N, 3 * EMBED)
-    assert dout.dtype == qkv.dtype and dout.shape == (B * N, EMBED), (dout.dtype, tuple(dout.shape))
-    assert w.dtype == torch.float32 and w.dim() == 3 and w.shape[0] == B and w.shape[2] == N and 1 <= w.shape[1] <= 8, tuple(w.shape)
-    R = w.shape[1]
-    q_rows = N if q_rows is None else q_rows
-    y = torch.empty((B, HEADS, R, N), dtype=torch.float32, device=qkv.device)
-    lse2 = torch.empty((B, HEADS, N), dtype=torch.float32, device=qkv.device)      # workspace: rows < q_rows are written
-    code = ((BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3)) | _lib.ATTN_APPLY | _lib.ATTN_APPLY_GRAD | _lib.ATTN_APPLY_HEADS
-            | _lib.attn_apply_rows(R))
-    # (work: the score product, formed twice, and the dP product)
-    _timed_call("maest_attn_relevance_heads", _attn_flops(B, N, q_rows, 6.0), _p(qkv), _p(dout), _p(w), None, _p(lse2), _p(y), B, N, code,
-                scale, q_rows, _s(qkv), _entry="maest_attn_bwd_rows")
-    return y
+    return _attn_pool(True, True, qkv, dout, w, B, N, scale, q_rows, x3, q_prescaled)
 
 
 _TWELFTH = float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(12.0, dtype=torch.float32))   # fp32(1 / 12), the kernels' constant
@@ -539,7 +514,7 @@ def attn_bwd(qkv, out, dout, lse, B: int, N: int, scale: float, q_rows=None, x3:
     """`delta` (fp32 [B, 12, N] = rowsum(dO * O), from gemm_nt_rowdot) given: `out` is not needed (pass None).
     q_prescaled (bf16 only): the q columns of `qkv` hold scale * log2(e) * q (MAEST_BF16_QS); dQ is still d / d(true q)."""
     _chk(qkv, out, dout, lse, delta)
-    assert not q_prescaled or (qkv.dtype == torch.bfloat16 and not x3)
+    code = _attn_code(qkv, x3, q_prescaled)
     assert dout.dtype == qkv.dtype and (out is None or out.dtype == qkv.dtype)
     if delta is None:
         assert out is not None
@@ -549,7 +524,7 @@ def attn_bwd(qkv, out, dout, lse, B: int, N: int, scale: float, q_rows=None, x3:
         out = None
     dqkv = torch.empty_like(qkv)
     _timed_call("maest_attn_bwd", _attn_flops(B, N, q_rows, 10.0), _p(qkv), _p(out), _p(dout), _p(lse),
-                _p(delta), _p(dqkv), B, N, BF16_QS if q_prescaled else _mm_code(qkv.dtype, x3), scale,
+                _p(delta), _p(dqkv), B, N, code, scale,
                 N if q_rows is None else q_rows, _s(qkv),
                 _entry="maest_attn_bwd_rows")
     return dqkv
